@@ -22,6 +22,12 @@ the same step on ONE stream with every launch bracketed (`--kernel-events all` p
 `dropin_api_ms_per_step` times the same step through the reference's calling convention
 (temporally_enhance_features on lists of fp32 NCHW frame tensors, model.py:157-158,340), i.e. including the
 fp32-NCHW -> bf16 layout pass that a train.py caller pays on every call.
+Plain run vs `--full`: a plain run sets up, warms up, times the steps and prints the line (its `roofline` comes from the
+events of the timed region, so it costs no run of its own).  The passes behind the timed region -- the per-layer tables,
+`dropin_api_ms_per_step` and `cpu_baseline` (minutes of host time) -- run only with `--full`; in a plain run those
+fields are null or hold only the dominant kernel.
+`--dump-outputs DIR` writes what the timed path computed in its last step (loss, fused maps, parameters and BN buffers,
+flat gradient) as DIR/<name>.npy right after the timed region, before any pass of `--full` moves the parameters on.
 """
 import argparse
 import json
@@ -74,6 +80,12 @@ def parse():
                     help='create the RCCL (nccl) process group even with ONE rank and send the gradient buckets through it '
                          '(an all-reduce over one rank is the identity): the RCCL path of the exchange on a single GPU')
     ap.add_argument('--master-port', type=int, default=29541)
+    ap.add_argument('--full', action='store_true',
+                    help='also run the passes behind the timed region: the one-stream per-layer tables, the drop-in API '
+                         'timing and the CPU baseline (a plain run does only what the headline figure needs)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the timed path computed in its last step as DIR/<name>.npy (float32; arrays of '
+                         'more than %d elements as a fixed, seeded sample)' % DUMP_SAMPLE)
     return ap.parse_args()
 
 
@@ -166,6 +178,31 @@ def make_step(model, opt, bucket, loss_fn, forward):
     return step
 
 
+DUMP_SAMPLE = 1 << 21    # elements kept of a larger array by --dump-outputs
+DUMP_LIMIT = 64 << 20    # bytes of all --dump-outputs files together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: name -> tensor, written as <path>/<name>.npy in float32 (float64 for integer buffers).  An array
+    of more than DUMP_SAMPLE elements is written as its flattened values at DUMP_SAMPLE positions drawn by a fixed seed
+    (ascending order): the same positions in every run and every build of the same arguments."""
+    import numpy as np
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        a = (t.float() if t.is_floating_point() else t.double()).cpu().numpy()
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(63).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx]
+        out[name] = a
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError('--dump-outputs: %d bytes exceed the limit of %d' % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def main_fp8(args):
     """BASELINE config 5: the e4m3 conv path, eval-mode FORWARD of one (sp, fp) clip over the DAVIS
     pyramid -- fast_conv1 and slow_conv1-3 (99 % of the forward FLOPs) on v_mfma_scale_f32_32x32x64_f8f6f4 with e4m3
@@ -201,20 +238,24 @@ def main_fp8(args):
             timer.reset()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for _ in range(steps):
+            for _ in range(steps - 1):
                 model.enhance_packed(clip)
+            merged = model.enhance_packed(clip)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
         k = timer.summary()
         model._timer = None
-        return dt, k
+        return dt, k, merged
 
-    dt, kdom = run('fp8', clip8, args.steps, args.warmup, ['conv_fwd/f1'])
+    dt, kdom, merged = run('fp8', clip8, args.steps, args.warmup, ['conv_fwd/f1'])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'out.' + k: v for k, v in merged.items()})
+    del merged
     model.n_streams = 1
-    _, k8 = run('fp8', clip8, 6, 2, None)
-    _, k16 = run('bf16', clip16, 6, 2, None)
+    _, k8, _ = run('fp8', clip8, 6, 2, None)
+    _, k16, _ = run('bf16', clip16, 6, 2, None)
     model.n_streams = args.streams
-    dt16, _ = run('bf16', clip16, args.steps, args.warmup, [])
+    dt16, _, _ = run('bf16', clip16, args.steps, args.warmup, [])
     plan = model.plan
     l = plan.layer('f1')
     fl = plan.layer_flops(P)
@@ -318,6 +359,13 @@ def main():
         sys.exit('--graph: one rank without --force-dist, and not with --kernel-events all')
     timer = model.enable_kernel_timer(None if args.kernel_events == 'all' else
                                       (['conv_fwd/f1'] if args.kernel_events == 'dominant' and not args.graph else []))
+    last = {}   # --dump-outputs: the fused maps and loss of the latest step (under --graph: the graph's static ones)
+    if args.dump_outputs:
+        proxy_loss = loss_fn
+
+        def loss_fn(merged):
+            last['merged'], last['loss'] = merged, proxy_loss(merged)
+            return last['loss']
     step = make_step(model, opt, bucket, loss_fn, lambda: model.enhance_packed(clip))
     run = step
     if args.graph:
@@ -345,8 +393,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     kern_dom = timer.summary()  # name -> (calls, mean ms): the timed region's own events
+    if args.dump_outputs and rank == 0:
+        arrays = {'loss': last['loss']}
+        arrays.update(('out.' + k, v) for k, v in last['merged'].items())
+        arrays.update(('state.' + k, v) for k, v in model.state_dict().items())
+        arrays['grad'] = opt.flat_grad
+        dump_outputs(args.dump_outputs, arrays)
+    last.clear()
     kern, table_steps = kern_dom, args.steps
-    if args.kernel_events != 'all' and not args.no_layer_table:
+    if args.full and args.kernel_events != 'all' and not args.no_layer_table:
         # per-layer table: the same step with every launch bracketed, outside the timed region
         table_steps = max(2, min(args.steps, 10)) // 2 * 2
         model.n_streams = 1   # one stream: every kernel runs alone, its event duration is its own
@@ -359,7 +414,7 @@ def main():
 
     # ---- the same step through the reference's calling convention: lists of fp32 NCHW frames -> layout pass inside
     dropin_ms = None
-    if not args.no_dropin and world == 1:
+    if args.full and not args.no_dropin and world == 1:
         from collections import OrderedDict
         fast = OrderedDict((k, torch.randn((args.fp, 256, h, w), generator=gen, device=dev)) for k, (h, w) in pyr)
         idx = args.fp // 2
@@ -466,7 +521,7 @@ def main():
             'hbm_layers': hbm_layers,
             'kernels_ms': {k: [v[0], round(v[1], 4)] for k, v in sorted(kern.items(), key=lambda kv: -kv[1][0] * kv[1][1])[:28]},
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line['cpu_baseline'] = cpu_baseline(args.sp, args.fp, args.cpu_threads, args.cpu_clips)
         else:
             line['cpu_baseline'] = None

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 P=gpurun_out/prof_r02
 rm -rf $P; mkdir -p $P
-BENCH="python3 bench.py --no-cpu-baseline --no-dropin"
+BENCH="python3 bench.py --full --no-cpu-baseline --no-dropin"
 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -- $BENCH --steps 10 --warmup 4 > $P/trace.log 2>&1
 # the same with ONE stream: per-kernel durations of kernels that run alone (with two streams a small kernel queued behind
 # the other stream's full-chip kernel waits for a free CU, and rocprof counts that wait as its duration)

@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 P=gpurun_out/prof_r03
 rm -rf $P; mkdir -p $P
-BENCH="python3 bench.py --no-cpu-baseline --no-dropin"
+BENCH="python3 bench.py --full --no-cpu-baseline --no-dropin"
 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -- $BENCH --steps 10 --warmup 4 > $P/trace.log 2>&1
 f=$(ls $P/trace/*/*kernel_stats.csv | head -1); cp $f $P/kernel_stats.csv
 echo "trace done" >> $P/progress.log
@@ -44,8 +44,8 @@ for name in sorted(out, key=lambda n: -out[n].get('FETCH_SIZE', {}).get('max', 0
 PY
 $BENCH --steps 20 --warmup 5 > $P/bench_line.json 2> $P/bench_line.err; tail -c 300 $P/bench_line.json
 # configuration 4: (sp, fp) = (4, 64)
-python3 bench.py --sp 4 --fp 64 --steps 10 --warmup 3 --no-cpu-baseline > $P/c4_bench_line.json 2> $P/c4_bench_line.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $P/c4trace -- python3 bench.py --sp 4 --fp 64 --streams 1 --steps 6 --warmup 2 --no-cpu-baseline --no-dropin > $P/c4trace.log 2>&1
+python3 bench.py --full --sp 4 --fp 64 --steps 10 --warmup 3 --no-cpu-baseline > $P/c4_bench_line.json 2> $P/c4_bench_line.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $P/c4trace -- python3 bench.py --full --sp 4 --fp 64 --streams 1 --steps 6 --warmup 2 --no-cpu-baseline --no-dropin > $P/c4trace.log 2>&1
 f=$(ls $P/c4trace/*/*kernel_stats.csv | head -1); cp $f $P/c4_kernel_stats_1stream.csv
 echo "c4 done" >> $P/progress.log
 # configuration 5: e4m3 conv path, eval forward

@@ -1,7 +1,8 @@
 #!/bin/bash
 cd $GRAFT_REPO_ROOT
+OUT_DIR=${OUT_DIR:-out}; mkdir -p $OUT_DIR
 C=$GRAFT_REPO_ROOT/applying-slowfast-networks-to-video-object-segmentation_amd/csrc
-OUT=gpurun_out/ab_tall.log; : > $OUT
+OUT=$OUT_DIR/ab_tall.log; : > $OUT
 for i in 1 2 3; do
   for L in libsfvos.so libsfvos_notall.so; do
     echo "== $L" >> $OUT
@@ -12,12 +13,12 @@ for i in 1 2 3; do
   done
 done
 grep -v amdgpu.ids $OUT
-OUT=gpurun_out/lwg_bench.log; : > $OUT
+OUT=$OUT_DIR/lwg_bench.log; : > $OUT
 for G in 1 2 4; do
-  SFVOS_LIB=$C/libsfvos_diag.so SFVOS_LWG_GROUPS=$G python bench.py --no-cpu-baseline --no-dropin --steps 6 --warmup 2 > gpurun_out/b_g$G.json 2>> $OUT
+  SFVOS_LIB=$C/libsfvos_diag.so SFVOS_LWG_GROUPS=$G python bench.py --full --no-cpu-baseline --no-dropin --steps 6 --warmup 2 > $OUT_DIR/b_g$G.json 2>> $OUT
   python - <<PY >> $OUT
 import json
-d=json.loads(open('gpurun_out/b_g$G.json').read().strip().splitlines()[-1])
+d=json.loads(open('$OUT_DIR/b_g$G.json').read().strip().splitlines()[-1])
 print('G $G', {k:v['ms'] for k,v in d['hbm_layers'].items() if 'wgrad' in k})
 PY
 done
