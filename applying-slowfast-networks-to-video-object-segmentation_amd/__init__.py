@@ -9,6 +9,7 @@ from .module import PackedClip, SlowFastLayers, union_mask  # noqa: F401
 from .optim import FusedSGD  # noqa: F401
 from .losses import MSEProxyLoss  # noqa: F401
 from .stream import SlowFastStream  # noqa: F401
+from .windows import SlowFastWindows  # noqa: F401
 from .mask_head import (MaskBranch, MaskRCNNHeads, MaskRCNNPredictor, maskrcnn_inference,  # noqa: F401
                         maskrcnn_loss, paste_masks_in_image)
 from .parallel import GradBucket, init_distributed  # noqa: F401
@@ -16,5 +17,5 @@ from .roi_align import MultiScaleRoIAlign, roi_align  # noqa: F401
 from .graph import GraphedStep  # noqa: F401
 
 __all__ = ['SlowFastLayers', 'PackedClip', 'SlowFastPlan', 'FusedSGD', 'GradBucket', 'init_distributed',
-           'MSEProxyLoss', 'calc_kernel_sizes', 'calc_fuse_kernel_size', 'davis_pyramid', 'union_mask', 'SlowFastStream', 'MaskBranch', 'MaskRCNNHeads', 'MaskRCNNPredictor',
+           'MSEProxyLoss', 'calc_kernel_sizes', 'calc_fuse_kernel_size', 'davis_pyramid', 'union_mask', 'SlowFastStream', 'SlowFastWindows', 'MaskBranch', 'MaskRCNNHeads', 'MaskRCNNPredictor',
            'maskrcnn_inference', 'maskrcnn_loss', 'paste_masks_in_image', 'MultiScaleRoIAlign', 'roi_align', 'GraphedStep']

@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SFVOS_LIB') or os.path.join(_HERE, 'csrc', 'libsfvos.so')  # SFVOS_LIB: A/B builds
 
 F32, BF16, FP8 = 0, 1, 2
-ABI_REVISION = 300   # the revision of include/sfvos.h this binding mirrors
+ABI_REVISION = 301   # the revision of include/sfvos.h this binding mirrors
 MAX_LEVELS = 8
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -107,6 +107,8 @@ SIGNATURES = {
     'sfvos_pack_weights_batch': (i32, [C.POINTER(PackItem), i32, i32, vp]),
     'sfvos_conv3d_stat_rows': (i32, [PD, C.POINTER(i32)]),
     'sfvos_conv3d': (i32, [PD, vp, vp, vp, vp, vp, vp]),
+    'sfvos_shift_frames_stat_rows': (i32, [C.POINTER(Pyramid), i32, i32, i32, C.POINTER(i32)]),
+    'sfvos_shift_frames': (i32, [vp, vp, vp, i32, C.POINTER(Pyramid), i32, i32, i32, i32, i32, vp, vp]),
     'sfvos_conv3d_wgrad_workspace_bytes': (C.c_size_t, [PD]),
     'sfvos_conv3d_wgrad': (i32, [PD, vp, vp, vp, i32, vp, vp]),
     'sfvos_bn_finalize': (i32, [vp, i32, C.POINTER(i32), C.POINTER(i64), vp, vp, f32, i32, vp, vp, vp, vp, vp, i32, vp]),

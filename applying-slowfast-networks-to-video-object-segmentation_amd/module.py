@@ -182,6 +182,20 @@ def _lv_total(lv):
     return sum(lv.m[i] for i in range(lv.n_levels))
 
 
+class RawReuse(object):
+    """First-layer reuse hook of SlowFastLayers._engine_forward (SlowFastWindows).
+
+    prev: layer name ('f1' / 's1') -> (raw buffer of the previous window, shift s), 1 <= s < the layer's t_out: the
+          layer computes only its s newest output frames and takes the other t_out - s from the previous window
+          (sfvos_shift_frames), whose statistics rows replace the conv's.
+    raw:  filled by the engine: 'f1' / 's1' -> the pre-BN buffer of this window (what the next window reuses)."""
+    __slots__ = ('prev', 'raw')
+
+    def __init__(self, prev=None):
+        self.prev = dict(prev or {})
+        self.raw = {}
+
+
 class SlowFastLayers(nn.Module):
     def __init__(self, input_size, device, slow_pathway_size, fast_pathway_size, precision=None):
         super(SlowFastLayers, self).__init__()
@@ -389,9 +403,12 @@ class SlowFastLayers(nn.Module):
         return layer.name[0] in 'sl'
 
     # ------------------------------------------------------------------ forward engine (whole pyramid)
-    def _engine_forward(self, shapes, B, xf0, xs0, slow_offset, keep, x_frames=None, x_pad=0):
+    def _engine_forward(self, shapes, B, xf0, xs0, slow_offset, keep, x_frames=None, x_pad=0, reuse=None):
         """xf0 / xs0: flat pyramid buffers [B*T*sum(HW), C] in the compute dtype (xs0 None when the slow
         clip aliases frames [slow_offset, slow_offset+sp) of the fast clip).
+        reuse: optional RawReuse -- fast_conv1 / slow_conv1 shift the previous window's pre-BN frames instead of
+        recomputing them.  Their BatchNorm statistics then come from the STORED values (sfvos_shift_frames' rows:
+        rounded to bf16 in bf16 mode), where the plain path sums the conv's f32 accumulators.
         Returns (list of merged [B,256,H,W] fp32 per level, state or None)."""
         plan = self.plan
         fp8 = self.precision == 'fp8'
@@ -402,6 +419,14 @@ class SlowFastLayers(nn.Module):
         if fp8 and (self.training or keep):
             raise RuntimeError("precision='fp8' is inference-only (eval mode, no autograd state): the e4m3 path has "
                                "no backward in this build")
+        if fp8 and reuse is not None:
+            raise RuntimeError("precision='fp8' has no first-layer reuse")
+        shift = {}   # layer -> (previous raw buffer, s)
+        for name, (prev, s) in (reuse.prev.items() if reuse is not None else ()):
+            l = self.plan.layer(name)
+            if name not in ('f1', 's1') or not 1 <= s < l.t_out:
+                raise ValueError('reuse: layer %r with shift %d (needs f1 / s1 and 1 <= s < %d)' % (name, s, l.t_out))
+            shift[name] = (prev, int(s))
         pix = sum(h * w for h, w in shapes)
         pyr = _lib.make_pyramid(shapes)
         bufs = {'xf0': xf0}
@@ -438,14 +463,30 @@ class SlowFastLayers(nn.Module):
                 d = self._desc(l, B, pyr, dt_id, src, l.c_out, t_alloc, t_off)
                 w = dict(d=d, lv=lv, src=src, wp=self._packed(l, 'fwd', dt_name),
                          cf=torch.empty((L, _CF_ROWS, l.c_out), dtype=torch.float32, device=dev))
+            if l.name in shift:
+                # the s newest output frames only: the conv's window starts t_out - s frames later and is s + kt - 1
+                # frames long; its result goes to a scratch buffer the shift appends behind the reused frames
+                prev, s = shift[l.name]
+                if prev.shape != bufs[l.raw].shape or prev.dtype != tdt or prev.device != dev \
+                        or not prev.is_contiguous():
+                    raise ValueError('reuse: previous %s must be a contiguous %s %s tensor on %s'
+                                     % (l.raw, tuple(bufs[l.raw].shape), tdt, dev))
+                d = self._desc(l, B, pyr, dt_id, src, l.c_out, d.t_alloc, d.t_offset + l.t_out - s)
+                d.t_in = s + l.kt - 1
+                w.update(d=d, prev=prev, s=s,
+                         fresh=torch.empty((B * s * pix, l.c_out), dtype=tdt, device=dev))
             if train:
                 if min(lv.m[i] for i in range(L)) <= 1:
                     raise ValueError('Expected more than 1 value per channel when training, got input size %s'
                                      % str([B, l.c_out, l.t_out] + list(shapes[-1])))
                 w['rows_pl'] = (ctypes.c_int * _lib.MAX_LEVELS)()
-                rows = lib.sfvos_conv3d_stat_rows(ctypes.byref(d), w['rows_pl'])
+                if 'prev' in w:
+                    rows = lib.sfvos_shift_frames_stat_rows(ctypes.byref(pyr), B, l.t_out, l.c_out, w['rows_pl'])
+                else:
+                    rows = lib.sfvos_conv3d_stat_rows(ctypes.byref(d), w['rows_pl'])
                 if rows <= 0:
-                    _lib.check(rows if rows < 0 else -1, 'sfvos_conv3d_stat_rows')
+                    _lib.check(rows if rows < 0 else -1, 'sfvos_shift_frames_stat_rows' if 'prev' in w
+                               else 'sfvos_conv3d_stat_rows')
                 w['rows'] = rows
                 w['part'] = torch.empty((rows, 2, l.c_out), dtype=torch.float32, device=dev)
             work[l.name] = w
@@ -480,10 +521,19 @@ class SlowFastLayers(nn.Module):
                     if l.name == 'l2' and 'f2' in ev:
                         stream.wait_event(ev['f2'])
                 run = None   # running-statistics update of this layer (training), folded into its BN-apply launch
-                if train:
+                if 'prev' in w:   # reuse: s new frames, then the shift writes raw (and, training, the statistics rows)
                     with self._t('conv_fwd', l.name):
-                        _lib.call('sfvos_conv3d', ctypes.byref(d), _ptr(src), _ptr(wp), bias, _ptr(raw),
-                                  _ptr(w['part']), st)
+                        _lib.call('sfvos_conv3d', ctypes.byref(d), _ptr(src), _ptr(wp), bias, _ptr(w['fresh']), None,
+                                  st)
+                    with self._t('shift', l.name):
+                        _lib.call('sfvos_shift_frames', _ptr(w['prev']), _ptr(w['fresh']), _ptr(raw), dt_id,
+                                  ctypes.byref(pyr), B, l.t_out, w['s'], l.c_out, l.c_out,
+                                  _ptr(w['part']) if train else None, st)
+                if train:
+                    if 'prev' not in w:
+                        with self._t('conv_fwd', l.name):
+                            _lib.call('sfvos_conv3d', ctypes.byref(d), _ptr(src), _ptr(wp), bias, _ptr(raw),
+                                      _ptr(w['part']), st)
                     if side is not None and self.f1_alone and l.name == 'f1':
                         e0 = torch.cuda.Event()
                         e0.record(stream)
@@ -503,8 +553,9 @@ class SlowFastLayers(nn.Module):
                         run.n_updates, run.momentum = L, float(bn.momentum)
                         run = ctypes.byref(run)
                 else:
-                    with self._t('conv_fwd', l.name):
-                        _lib.call('sfvos_conv3d', ctypes.byref(d), _ptr(src), _ptr(wp), bias, _ptr(raw), None, st)
+                    if 'prev' not in w:
+                        with self._t('conv_fwd', l.name):
+                            _lib.call('sfvos_conv3d', ctypes.byref(d), _ptr(src), _ptr(wp), bias, _ptr(raw), None, st)
                     _lib.call('sfvos_bn_eval_coeffs', _ptr(bn.weight.detach()), _ptr(bn.bias.detach()),
                               _ptr(bn.running_mean), _ptr(bn.running_var), float(bn.eps), l.c_out, _ptr(cf[0, _MEAN]),
                               _ptr(cf[0, _RSTD]), _ptr(cf[0, _SCALE]), _ptr(cf[0, _SHIFT]), st)
@@ -525,6 +576,9 @@ class SlowFastLayers(nn.Module):
             coef[l.name] = cf
         if side is not None:
             main.wait_stream(side)
+
+        if reuse is not None:
+            reuse.raw = {n: bufs[plan.layer(n).raw] for n in ('f1', 's1')}
 
         # -- cat([slow224, fast32], 1).squeeze(2) (model.py:162) as the caller's NCHW fp32 tensors
         st = _stream()
@@ -869,7 +923,8 @@ class _SlowFastPyramidFn(torch.autograd.Function):
         x_frames, x_pad = meta.get('x_frames'), meta.get('x_pad', 0)
         if x_frames == module.plan.fp and x_pad == 0:
             x_frames = None   # the whole window is stored
-        merged, state = module._engine_forward(shapes, B, xf0, xs0, slow_offset, keep, x_frames, x_pad)
+        merged, state = module._engine_forward(shapes, B, xf0, xs0, slow_offset, keep, x_frames, x_pad,
+                                               meta.get('reuse'))
         ctx.module, ctx.state, ctx.names, ctx.mode, ctx.n_in, ctx.L = module, state, names, meta['mode'], n_in, L
         return tuple(merged)
 

@@ -66,7 +66,8 @@ typedef struct sfvos_levels {
 /* ABI revision: 100 = round 1; 200 = struct_size in sfvos_conv_desc, no `zeros` argument, sfvos_abi_sizes,
  * sfvos_add_inplace, sfvos_mse_loss / _grad, mask-head entry points; 201 = sfvos_bn_running argument of the BN-apply
  * calls, mask-branch training entry points, sfvos_pack_weights_batch, sfvos_pyramid_to_frames / sfvos_frames_to_pyramid;
- * 300 (round 3) = sfvos_roi_levels / sfvos_roi_align / sfvos_roi_align_bwd (+ workspace query). */
+ * 300 (round 3) = sfvos_roi_levels / sfvos_roi_align / sfvos_roi_align_bwd (+ workspace query); 301 =
+ * sfvos_shift_frames / sfvos_shift_frames_stat_rows (first-layer reuse across consecutive training windows). */
 int sfvos_version(void);
 /* sizes[0..n) = sizeof(sfvos_conv_desc), sizeof(sfvos_pyramid), sizeof(sfvos_levels), sizeof(sfvos_mse_table),
  * sizeof(sfvos_bn_running), sizeof(sfvos_pack_item), sizeof(sfvos_planar_level) as THIS library was compiled; returns
@@ -218,6 +219,21 @@ int sfvos_conv3d_stat_rows(const sfvos_conv_desc* d, int* rows_per_level);
  * check (frames outside [0, t_in) and pixels outside the image are never read). */
 int sfvos_conv3d(const sfvos_conv_desc* d, const void* x, const void* w_packed, const float* bias, void* y,
                  float* stat_part, sfvos_stream_t stream);
+
+/* ---- window shift (SlowFastWindows: consecutive centre frames of the reference's training loop, model.py:316-374) ----
+ * The pre-BatchNorm output of a first-layer conv depends only on the weights and the input frames, so the window one
+ * centre frame later is the previous window's frames s .. T-1 followed by s new frames.  For every level l, clip b and
+ * frame t of level-major pyramid buffers with pitch ld (first C channels):
+ *     out[l][b][t] = prev[l][b][t + s]             t <  T - s
+ *     out[l][b][t] = fresh[l][b][t - (T - s)]      t >= T - s   (fresh: a pyramid buffer of s frames, pitch ld)
+ * stat_part (may be NULL): partial (sum, sum of squares) rows [rows][2][C] fp32 of the values written, level-major as
+ * the rows of sfvos_conv3d_stat_rows, to be reduced by the BatchNorm finalize (fixed order, deterministic).
+ * dtype f32 or bf16; C a multiple of 32, <= 256; 1 <= s < T; out must not overlap prev or fresh (never in place). */
+
+/* Rows of stat_part for these dims: returns the total and, when rows_per_level != NULL, the count per level. */
+int sfvos_shift_frames_stat_rows(const sfvos_pyramid* pyr, int B, int T, int C, int* rows_per_level);
+int sfvos_shift_frames(const void* prev, const void* fresh, void* out, int dtype, const sfvos_pyramid* pyr, int B, int T,
+                       int s, int C, int ld, float* stat_part, sfvos_stream_t stream);
 
 /* ---- weight gradient (aten::convolution_backward grad_weight / grad_bias) -------------- */
 
