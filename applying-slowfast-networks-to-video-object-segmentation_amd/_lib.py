@@ -189,8 +189,8 @@ def call(name, *args):
     check(getattr(load(), name)(*args), name)
 
 
-# Bumped by anything that rewrites parameters behind autograd's back (FusedSGD); the packed
-# MFMA weight images cached by SlowFastLayers are keyed on it.
+# Bumped by anything that rewrites parameters behind autograd's back (FusedSGD); every packed
+# weight image (WeightImages) is tagged with it.
 _weight_epoch = [0]
 
 
@@ -200,3 +200,45 @@ def bump_weight_epoch():
 
 def weight_epoch():
     return _weight_epoch[0]
+
+
+def weight_tag(params):
+    """What identifies the values of `params` (None entries skipped) between two calls: (_version, data_ptr) of
+    each -- autograd, torch.optim.SGD.step and load_state_dict bump _version, `.data =` gives a new storage -- and
+    the weight epoch, for FusedSGD, which writes through raw pointers."""
+    tag = [_weight_epoch[0]]
+    for p in params:
+        if p is not None:
+            tag += (p._version, p.data_ptr())
+    return tag
+
+
+class WeightImages(object):
+    """Cache of packed weight images.  The caller names each image by a key and says which parameters it is built
+    from; an image is rebuilt when their weight_tag changed since it was packed."""
+
+    def __init__(self):
+        self._images = {}   # key -> (weight_tag when packed, image)
+
+    def get(self, key, params, pack, *args):
+        """The image of `key`; pack(*args) builds it when it is missing or stale."""
+        tag = weight_tag(params)
+        hit = self._images.get(key)
+        if hit is not None and hit[0] == tag:
+            return hit[1]
+        image = pack(*args)
+        self._images[key] = (tag, image)
+        return image
+
+    def stale(self, key, params):
+        """True for an image that was packed before and no longer matches `params`."""
+        hit = self._images.get(key)
+        return hit is not None and hit[0] != weight_tag(params)
+
+    def put(self, key, params, image):
+        self._images[key] = (weight_tag(params), image)
+
+    def mark_stale(self):
+        """Every image is rebuilt on its next use; the entries stay, so that `stale` still finds them."""
+        for key, (_, image) in list(self._images.items()):
+            self._images[key] = (None, image)

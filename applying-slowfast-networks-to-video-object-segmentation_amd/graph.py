@@ -73,8 +73,7 @@ class GraphedStep(object):
                 if k == 0:
                     # the first graph of a cycle re-packs every weight image, whatever happened before it: mark the cached
                     # ones stale (the entries stay, so that the first miss refreshes them all in ONE batched launch)
-                    for key, (_, img) in list(model._packs.items()):
-                        model._packs[key] = (None, img)
+                    model._images.mark_stale()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, stream=side):
                     loss = self._clip_step(k)

@@ -10,10 +10,7 @@ import ctypes
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+from .module import _ptr, _stream
 
 
 def _table(outs, targets, grads=None):
@@ -41,7 +38,7 @@ class _MseFn(torch.autograd.Function):
         dev = outs[0].device
         part = torch.empty(rows, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        st = _stream()
         _lib.call('sfvos_mse_loss', ctypes.byref(tab), _ptr(part), _ptr(loss), st)
         ctx.outs, ctx.targets, ctx.n = outs, targets, n
         return loss
@@ -53,7 +50,7 @@ class _MseFn(torch.autograd.Function):
         tab = _table(outs, targets, grads)
         g = g.detach()
         up = g if (g.dtype == torch.float32 and g.is_cuda) else g.to(outs[0].device, torch.float32)
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        st = _stream()
         _lib.call('sfvos_mse_loss_grad', ctypes.byref(tab), _ptr(up), st)
         return (None,) + tuple(grads) + (None,) * ctx.n
 

@@ -22,7 +22,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .module import _DT, _ptr, _stream
+from .module import _DT, _conv_desc, _ptr, _stream
 
 
 def _check_gpu(t, what):
@@ -39,6 +39,14 @@ def _to_nhwc(x, dt_id, tdt):
     _lib.call('sfvos_frames_to_ndhwc', _ptr(s), s.stride(0), s.stride(1), s.stride(2), s.stride(3), _ptr(out), dt_id,
               N, C, H, W, C, _stream())
     return out
+
+
+def _pack(fn, w, dt_id, tdt, *shape):
+    """Packed image of weight w (fp32 copy) by the libsfvos packer fn (shape: its size arguments)."""
+    wc = w.detach().float().contiguous()
+    packed = torch.empty(wc.numel(), dtype=tdt, device=w.device)
+    _lib.call(fn, _ptr(wc), _ptr(packed), dt_id, *(shape + (_stream(),)))
+    return packed
 
 
 def _to_nchw(x_nhwc, dt_id):
@@ -69,22 +77,12 @@ class MaskRCNNHeads(nn.Module):
         for name, p in self.named_parameters():   # torchvision's init
             if 'weight' in name:
                 nn.init.kaiming_normal_(p, mode='fan_out', nonlinearity='relu')
-        self._packs = {}
+        self._images = _lib.WeightImages()
 
     def _packed(self, conv, dt_id, tdt, dgrad=False):
-        w = conv.weight
-        key = (id(conv), dgrad)
-        # weight_epoch: FusedSGD rewrites parameters through raw pointers (no autograd version bump), see module.py
-        tag = (w._version, w.data_ptr(), dt_id, _lib.weight_epoch())
-        hit = self._packs.get(key)
-        if hit is not None and hit[0] == tag:
-            return hit[1]
-        wc = w.detach().float().contiguous()
-        packed = torch.empty(wc.numel(), dtype=tdt, device=w.device)
-        _lib.call('sfvos_pack_weights_dgrad' if dgrad else 'sfvos_pack_weights_fwd', _ptr(wc), _ptr(packed), dt_id,
-                  conv.out_channels, conv.in_channels, 1, 9, _stream())
-        self._packs[key] = (tag, packed)
-        return packed
+        fn = 'sfvos_pack_weights_dgrad' if dgrad else 'sfvos_pack_weights_fwd'
+        return self._images.get((id(conv), fn, dt_id), (conv.weight,), _pack, fn, conv.weight, dt_id, tdt,
+                                conv.out_channels, conv.in_channels, 1, 9)
 
     def forward_nhwc(self, x, keep=False):
         """keep: return every activation [input, after mask_fcn1 + ReLU, ...] (channels-last) for the backward."""
@@ -95,7 +93,7 @@ class MaskRCNNHeads(nn.Module):
         acts = [cur]
         for i in range(1, self.n_layers + 1):
             conv = getattr(self, 'mask_fcn%d' % i)
-            d = _conv_desc(dt_id, N, H, W, conv.in_channels, conv.out_channels, 1)
+            d = _conv3x3_desc(dt_id, N, H, W, conv.in_channels, conv.out_channels, relu=1)
             y = torch.empty((N, H, W, conv.out_channels), dtype=tdt, device=x.device)
             bias = _ptr(conv.bias.detach()) if conv.bias is not None else None
             _lib.call('sfvos_conv3d', ctypes.byref(d), _ptr(cur), _ptr(self._packed(conv, dt_id, tdt)), bias, _ptr(y),
@@ -124,34 +122,23 @@ class MaskRCNNPredictor(nn.Module):
         for name, p in self.named_parameters():
             if 'weight' in name:
                 nn.init.kaiming_normal_(p, mode='fan_out', nonlinearity='relu')
-        self._pack = None
-        self._pack_d = None
+        self._images = _lib.WeightImages()
+
+    def _packed(self, dt_id, tdt, dgrad=False):
+        w = self.conv5_mask.weight
+        fn = 'sfvos_pack_deconv2x2_dgrad' if dgrad else 'sfvos_pack_deconv2x2'
+        return self._images.get((fn, dt_id), (w,), _pack, fn, w, dt_id, tdt, w.shape[0], w.shape[1])
 
     def _deconv_nhwc(self, x_nhwc):
         dt_id, tdt = _DT[self.precision]
         N, H, W, C = x_nhwc.shape
         w = self.conv5_mask.weight
-        tag = (w._version, w.data_ptr(), dt_id, _lib.weight_epoch())
-        if self._pack is None or self._pack[0] != tag:
-            wc = w.detach().float().contiguous()
-            packed = torch.empty(wc.numel(), dtype=tdt, device=w.device)
-            _lib.call('sfvos_pack_deconv2x2', _ptr(wc), _ptr(packed), dt_id, w.shape[0], w.shape[1], _stream())
-            self._pack = (tag, packed)
+        packed = self._packed(dt_id, tdt)
         y = torch.empty((N, 2 * H, 2 * W, w.shape[1]), dtype=tdt, device=x_nhwc.device)
         b = self.conv5_mask.bias
-        _lib.call('sfvos_deconv2x2_relu', _ptr(x_nhwc), _ptr(self._pack[1]), _ptr(b.detach()) if b is not None else None,
+        _lib.call('sfvos_deconv2x2_relu', _ptr(x_nhwc), _ptr(packed), _ptr(b.detach()) if b is not None else None,
                   _ptr(y), dt_id, N, H, W, w.shape[0], w.shape[1], 1, _stream())
         return y
-
-    def _packed_dgrad(self, dt_id, tdt):
-        w = self.conv5_mask.weight
-        tag = (w._version, w.data_ptr(), dt_id, _lib.weight_epoch())
-        if self._pack_d is None or self._pack_d[0] != tag:
-            wc = w.detach().float().contiguous()
-            packed = torch.empty(wc.numel(), dtype=tdt, device=w.device)
-            _lib.call('sfvos_pack_deconv2x2_dgrad', _ptr(wc), _ptr(packed), dt_id, w.shape[0], w.shape[1], _stream())
-            self._pack_d = (tag, packed)
-        return self._pack_d[1]
 
     def _logits(self, y_nhwc, labels=None, want_logits=True, want_prob=False):
         dt_id, _ = _DT[self.precision]
@@ -209,12 +196,9 @@ def paste_masks_in_image(masks, boxes, img_shape, padding=1):
     return out
 
 
-def _conv_desc(dt_id, N, H, W, c_in, c_out, relu):
-    d = _lib.ConvDesc()
-    d.dtype, d.batch, d.t_in, d.t_alloc, d.t_offset = dt_id, N, 1, 1, 0
-    d.c_in, d.c_out, d.kt, d.taps, d.pad_t = c_in, c_out, 1, 9, 0
-    d.ld_x, d.ld_y, d.accumulate, d.relu, d.pyr = c_in, c_out, 0, relu, _lib.make_pyramid([(H, W)])
-    return d
+def _conv3x3_desc(dt_id, N, H, W, c_in, c_out, relu=0):
+    """A 2-D 3x3 conv over N NHWC images: one frame (t_in = kt = 1) of a one-level pyramid, batch N."""
+    return _conv_desc(dt_id, N, _lib.make_pyramid([(H, W)]), 1, 9, c_in, c_out, 1, c_in, c_out, relu=relu)
 
 
 class _MaskBranchFn(torch.autograd.Function):
@@ -265,8 +249,8 @@ class _MaskBranchFn(torch.autograd.Function):
         _lib.call('sfvos_deconv2x2_wgrad', _ptr(acts[-1]), _ptr(dz), dt_id, N, H, W, ci5, co5, _ptr(g_w5), 0, _ptr(ws),
                   _stream())
         cur = torch.empty_like(acts[-1])
-        _lib.call('sfvos_deconv2x2_dgrad', _ptr(dz), _ptr(pred._packed_dgrad(dt_id, tdt)), _ptr(cur), dt_id, N, H, W,
-                  ci5, co5, _stream())
+        _lib.call('sfvos_deconv2x2_dgrad', _ptr(dz), _ptr(pred._packed(dt_id, tdt, dgrad=True)), _ptr(cur), dt_id, N, H,
+                  W, ci5, co5, _stream())
         tail = [g_w5, g_b5, g_wl, g_bl]
         # ---- mask_fcn{L..1}: ReLU backward (+ bias gradient), weight gradient, data gradient
         M = N * H * W
@@ -280,7 +264,7 @@ class _MaskBranchFn(torch.autograd.Function):
             _lib.call('sfvos_relu_bwd', _ptr(cur), _ptr(acts[i]), _ptr(cur), dt_id, M, cout, _ptr(rpart), _stream())
             g_b = torch.empty(cout, **f32)
             _lib.call('sfvos_reduce_rows', _ptr(rpart), rrows, cout, _ptr(g_b), 0, _stream())
-            d = _conv_desc(dt_id, N, H, W, cin, cout, 0)
+            d = _conv3x3_desc(dt_id, N, H, W, cin, cout)
             g_w = torch.empty(conv.weight.shape, **f32)
             wsz = lib.sfvos_conv3d_wgrad_workspace_bytes(ctypes.byref(d))
             wws = torch.empty(max(int(wsz), 16), dtype=torch.uint8, device=dev)
@@ -288,7 +272,7 @@ class _MaskBranchFn(torch.autograd.Function):
                       _stream())
             conv_grads.append((g_w, g_b))
             if i > 1 or need[1]:
-                dd = _conv_desc(dt_id, N, H, W, cout, cin, 0)
+                dd = _conv3x3_desc(dt_id, N, H, W, cout, cin)
                 nxt = torch.empty((N, H, W, cin), dtype=tdt, device=dev)
                 _lib.call('sfvos_conv3d', ctypes.byref(dd), _ptr(cur), _ptr(head._packed(conv, dt_id, tdt, dgrad=True)),
                           None, _ptr(nxt), None, _stream())

@@ -38,6 +38,33 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _conv_desc(dt_id, batch, pyr, kt, taps, c_in, c_out, t_in, x, ld_y, t_alloc=None, t_offset=0, pad_t=0,
+               accumulate=0, relu=0):
+    """sfvos_conv_desc.  x: pitch of the input in elements, or the input tensor itself ([M, ld] ndhwc, or
+    channel-group-major [C/32][M][32] bf16 / [C/64][M][64] e4m3); t_alloc defaults to t_in."""
+    d = _lib.ConvDesc()
+    if torch.is_tensor(x):
+        if x.dim() == 3:
+            d.x_group_stride, x = x.shape[1] * x.shape[2], x.shape[2]
+        else:
+            x = x.shape[-1]
+    d.dtype, d.batch, d.kt, d.taps, d.pyr = dt_id, batch, kt, taps, pyr
+    d.t_in, d.c_in, d.c_out, d.pad_t = t_in, c_in, c_out, pad_t
+    d.t_alloc, d.t_offset = (t_in if t_alloc is None else t_alloc), t_offset
+    d.ld_x, d.ld_y, d.accumulate, d.relu = x, ld_y, accumulate, relu
+    return d
+
+
+def _bn_eval_coeffs(bn, cf, st):
+    """Eval-mode BatchNorm coefficients (running statistics) into rows MEAN .. SHIFT of cf [levels, _CF_ROWS, C]:
+    computed for level 0, copied to the others (plumbing copy)."""
+    _lib.call('sfvos_bn_eval_coeffs', _ptr(bn.weight.detach()), _ptr(bn.bias.detach()), _ptr(bn.running_mean),
+              _ptr(bn.running_var), float(bn.eps), cf.shape[-1], _ptr(cf[0, _MEAN]), _ptr(cf[0, _RSTD]),
+              _ptr(cf[0, _SCALE]), _ptr(cf[0, _SHIFT]), st)
+    if cf.shape[0] > 1:
+        cf[1:, :4] = cf[0, :4]
+
+
 def _planar_levels(tensors):
     """sfvos_planar_level array for a list of [B,C,H,W] fp32 tensors (one per pyramid level)."""
     arr = (_lib.PlanarLevel * len(tensors))()
@@ -178,6 +205,32 @@ class _State(object):
     __slots__ = ('B', 'shapes', 'bufs', 'coef', 'train', 'dtype_name', 'slow_offset', 'x_frames', 'x_pad')
 
 
+class _FwdLayer(object):
+    """One layer of a forward pass: set up in phase 1 of _engine_forward, launched in phase 2.
+    prev / s / fresh only when the layer reuses the previous window (RawReuse); rows_pl / part only in training
+    (per-level row counts and buffer of the BatchNorm statistics partials)."""
+    __slots__ = ('l', 'd', 'lv', 'src', 'wp', 'bias', 'cf', 'prev', 's', 'fresh', 'rows_pl', 'part')
+
+    def __init__(self, l, d, lv, src, wp, bias, cf):
+        self.l, self.d, self.lv, self.src, self.wp, self.bias, self.cf = l, d, lv, src, wp, bias, cf
+        self.prev = self.fresh = self.rows_pl = self.part = None
+        self.s = 0
+
+
+class _BwdLayer(object):
+    """One layer of a backward pass: set up in phase 1 of _engine_backward, launched in phase 2.
+    wd / ws / gw only with need_w (weight gradient), dd / wpd only with need_in (data gradient), bpart / db only
+    with need_b (conv bias gradient)."""
+    __slots__ = ('l', 'lv', 'rows', 'need_in', 'need_w', 'need_b', 'part', 'dgamma', 'dbeta', 'dx', 'src',
+                 'wd', 'ws', 'gw', 'dd', 'wpd', 'bpart', 'db')
+
+    def __init__(self, l, lv, rows, need_in, need_w, need_b, part, dgamma, dbeta, dx, src):
+        self.l, self.lv, self.rows, self.part, self.dgamma, self.dbeta, self.dx, self.src = \
+            l, lv, rows, part, dgamma, dbeta, dx, src
+        self.need_in, self.need_w, self.need_b = need_in, need_w, need_b
+        self.wd = self.ws = self.gw = self.dd = self.wpd = self.bpart = self.db = None
+
+
 def _lv_total(lv):
     return sum(lv.m[i] for i in range(lv.n_levels))
 
@@ -223,7 +276,7 @@ class SlowFastLayers(nn.Module):
         self.fp8_input_scale = 32.0   # e4m3 activation scale of the input clip (|x| * scale must stay below 448)
         self.fp8_act_scale = 32.0     # ... of the slow pathway's concat buffers (post-ReLU BatchNorm outputs)
         self._fp8_sat = None          # device int: input elements that saturated in e4m3 since the last check
-        self._packs = {}     # (conv name, kind, dtype) -> ((param version, data_ptr, epoch), packed tensor)
+        self._images = _lib.WeightImages()   # (conv name, kind, dtype or e4m3 act scale) -> packed weight image
         self._timer = None
         self._timer_only = None
         self._side = None
@@ -277,7 +330,7 @@ class SlowFastLayers(nn.Module):
         ts = [(torch.stack([d[k] for d in fast_features]) if len(fast_features) > 1 else fast_features[0][k].unsqueeze(0))
               .transpose(1, 2) for k in keys]
         self._check_ready(ts[0])
-        data = self._to_pyramid_fp8(ts, ts[0].shape[2])
+        data = self._to_pyramid(ts, ts[0].shape[2], fp8=True)
         return PackedClip(data, [tuple(t.shape[3:]) for t in ts], ts[0].shape[0], ts[0].shape[2], keys)
 
     def _t(self, kind, layer):
@@ -299,50 +352,45 @@ class SlowFastLayers(nn.Module):
             raise RuntimeError('module parameters are on %s but inputs on %s' % (w.device, ref.device))
 
     def _packed(self, layer, kind, dt_name):
-        dt_id, tdt = _DT[dt_name]
-        w = getattr(self, layer.conv).weight
-        key = (layer.conv, kind, dt_name)
-        hit = self._packs.get(key)
-        tag = (w._version, w.data_ptr(), _lib.weight_epoch())
-        if hit is not None and hit[0] == tag:
-            return hit[1]
+        w = self._modules[layer.conv].weight   # = getattr(self, layer.conv), without nn.Module's slow lookup
+        return self._images.get((layer.conv, kind, dt_name), (w,), self._pack_batch, layer, w, kind, dt_name)
+
+    def _pack_batch(self, layer, w, kind, dt_name):
         # a miss: the weights changed (optimiser step).  Every image of this kind that has been used before is stale for
         # the same reason -- refresh them all in ONE launch (sfvos_pack_weights_batch) instead of one per layer
-        todo = [(layer, key, w, tag)]
+        dt_id, tdt = _DT[dt_name]
+        todo = [(layer, w)]
         for l2 in self.plan.layers:
-            k2 = (l2.conv, kind, dt_name)
-            if k2 == key or k2 not in self._packs:
-                continue
             w2 = getattr(self, l2.conv).weight
-            t2 = (w2._version, w2.data_ptr(), _lib.weight_epoch())
-            if self._packs[k2][0] != t2 and w2.device == w.device:
-                todo.append((l2, k2, w2, t2))
+            if l2 is not layer and w2.device == w.device and self._images.stale((l2.conv, kind, dt_name), (w2,)):
+                todo.append((l2, w2))
         todo = todo[:_lib.MAX_PACK_ITEMS]
         items = (_lib.PackItem * len(todo))()
         hold = []
-        for i, (l2, k2, w2, t2) in enumerate(todo):
+        for i, (l2, w2) in enumerate(todo):
             wc = w2.detach()
             if wc.dtype != torch.float32 or not wc.is_contiguous():
                 wc = wc.float().contiguous()
             img = torch.empty(w2.numel(), dtype=tdt, device=w2.device)
-            hold.append(wc)
+            hold.append((wc, img))
             items[i].w, items[i].packed = wc.data_ptr(), img.data_ptr()
             items[i].c_out, items[i].c_in, items[i].kt, items[i].taps = l2.c_out, l2.c_in, l2.kt, l2.taps
             items[i].dgrad = 0 if kind == 'fwd' else 1
-            self._packs[k2] = (t2, img)
+            if i:
+                self._images.put((l2.conv, kind, dt_name), (w2,), img)
         _lib.call('sfvos_pack_weights_batch', items, len(todo), dt_id, _stream())
-        return self._packs[key][1]
+        return hold[0][1]
 
     def _packed_fp8(self, layer, act_scale):
         """(e4m3 weight image, [3][c_out] (bias, descale, weight scale) rows) of a 3x3 layer whose input was quantised
         with act_scale, cached like _packed."""
         conv = getattr(self, layer.conv)
+        return self._images.get((layer.conv, 'fwd8', float(act_scale)), (conv.weight, conv.bias), self._pack_fp8,
+                                layer, conv, float(act_scale))
+
+    @staticmethod
+    def _pack_fp8(layer, conv, act_scale):
         w = conv.weight
-        key = (layer.conv, 'fwd8', float(act_scale))
-        hit = self._packs.get(key)
-        tag = (w._version, w.data_ptr(), _lib.weight_epoch(), None if conv.bias is None else conv.bias._version)
-        if hit is not None and hit[0] == tag:
-            return hit[1]
         packed = torch.empty(w.numel(), dtype=torch.uint8, device=w.device)
         bd = torch.empty((3, layer.c_out), dtype=torch.float32, device=w.device)
         wc = w.detach()
@@ -350,28 +398,8 @@ class SlowFastLayers(nn.Module):
             wc = wc.float().contiguous()
         bc = None if conv.bias is None else conv.bias.detach().float().contiguous()
         _lib.call('sfvos_pack_weights_fp8', _ptr(wc), _ptr(bc) if bc is not None else None, _ptr(packed), _ptr(bd),
-                  layer.c_out, layer.c_in, layer.kt, layer.taps, float(act_scale), _stream())
-        self._packs[key] = (tag, (packed, bd))
+                  layer.c_out, layer.c_in, layer.kt, layer.taps, act_scale, _stream())
         return packed, bd
-
-    def _desc(self, layer, B, pyr, dt_id, ld_x, ld_y, t_alloc=None, t_offset=0, dgrad=False, accumulate=0):
-        """ld_x: pitch of x in elements, or the x tensor itself ([M, ld] ndhwc / [G, M, 32] grouped)."""
-        d = _lib.ConvDesc()
-        d.x_group_stride = d.x_frame_stride = d.y_frame_stride = 0
-        if torch.is_tensor(ld_x):
-            if ld_x.dim() == 3:   # channel-group-major: [C/32][M][32] bf16 or [C/64][M][64] e4m3
-                d.x_group_stride, ld_x = ld_x.shape[1] * ld_x.shape[2], ld_x.shape[2]
-            else:
-                ld_x = ld_x.shape[-1]
-        d.dtype, d.batch, d.kt, d.taps, d.pyr = dt_id, B, layer.kt, layer.taps, pyr
-        if dgrad:  # conv over dy producing dx: channels swapped, full temporal padding
-            d.t_in, d.c_in, d.c_out, d.pad_t = layer.t_out, layer.c_out, layer.c_in, layer.kt - 1
-            d.t_alloc, d.t_offset = layer.t_out, 0
-        else:
-            d.t_in, d.c_in, d.c_out, d.pad_t = layer.t_in, layer.c_in, layer.c_out, 0
-            d.t_alloc, d.t_offset = (layer.t_in if t_alloc is None else t_alloc), t_offset
-        d.ld_x, d.ld_y, d.accumulate = ld_x, ld_y, accumulate
-        return d
 
     def _src_window(self, layer, slow_offset, x_frames=None, x_pad=0):
         """(buffer name, t_alloc, t_offset) of a layer's input.  The slow pathway's first conv reads its centre frames
@@ -439,7 +467,7 @@ class SlowFastLayers(nn.Module):
         # -- phase 1 (current stream): every buffer and workspace of the pass is allocated, and every weight
         # image packed, BEFORE the side stream is forked, and nothing is freed until the streams are joined,
         # so the caching allocator never hands memory still in use on one stream to the other.
-        work = {}
+        work = []
         # e4m3 path: the Cin = 256 3x3 convs take e4m3 operands -- the input clip (64-channel groups) and the slow
         # pathway's concat buffers, which BN-apply writes as e4m3 [M][256] directly; conv results stay bf16
         fp8_bufs = ('cat1', 'cat2') if fp8 else ()
@@ -453,65 +481,62 @@ class SlowFastLayers(nn.Module):
                                              dtype=torch.uint8 if name in fp8_bufs else tdt, device=dev)
             sname, t_alloc, t_off = self._src_window(l, slow_offset, x_frames, x_pad)
             src = bufs[sname]
-            lv = _lib.make_levels(shapes, B, l.t_out)
-            if fp8 and l.taps == 9 and l.c_in % 64 == 0:   # (bias, descale) rows travel as `bias`
-                d = self._desc(l, B, pyr, _lib.FP8, src, l.c_out, t_alloc, t_off)
-                wp, bd = self._packed_fp8(l, self.fp8_input_scale if sname == 'xf0' else self.fp8_act_scale)
-                w = dict(d=d, lv=lv, src=src, wp=wp, bias8=bd,
-                         cf=torch.empty((L, _CF_ROWS, l.c_out), dtype=torch.float32, device=dev))
-            else:
-                d = self._desc(l, B, pyr, dt_id, src, l.c_out, t_alloc, t_off)
-                w = dict(d=d, lv=lv, src=src, wp=self._packed(l, 'fwd', dt_name),
-                         cf=torch.empty((L, _CF_ROWS, l.c_out), dtype=torch.float32, device=dev))
-            if l.name in shift:
+            t_in, t_alloc = l.t_in, (l.t_in if t_alloc is None else t_alloc)
+            prev, s = shift.get(l.name, (None, 0))
+            if prev is not None:
                 # the s newest output frames only: the conv's window starts t_out - s frames later and is s + kt - 1
                 # frames long; its result goes to a scratch buffer the shift appends behind the reused frames
-                prev, s = shift[l.name]
                 if prev.shape != bufs[l.raw].shape or prev.dtype != tdt or prev.device != dev \
                         or not prev.is_contiguous():
                     raise ValueError('reuse: previous %s must be a contiguous %s %s tensor on %s'
                                      % (l.raw, tuple(bufs[l.raw].shape), tdt, dev))
-                d = self._desc(l, B, pyr, dt_id, src, l.c_out, d.t_alloc, d.t_offset + l.t_out - s)
-                d.t_in = s + l.kt - 1
-                w.update(d=d, prev=prev, s=s,
-                         fresh=torch.empty((B * s * pix, l.c_out), dtype=tdt, device=dev))
+                t_in, t_off = s + l.kt - 1, t_off + l.t_out - s
+            conv = getattr(self, l.conv)
+            e4m3 = fp8 and l.taps == 9 and l.c_in % 64 == 0
+            if e4m3:   # (bias, descale) rows travel as `bias`
+                wp, bias = self._packed_fp8(l, self.fp8_input_scale if sname == 'xf0' else self.fp8_act_scale)
+                bias = _ptr(bias)
+            else:
+                wp = self._packed(l, 'fwd', dt_name)
+                bias = _ptr(conv.bias.detach()) if conv.bias is not None else None
+            d = _conv_desc(_lib.FP8 if e4m3 else dt_id, B, pyr, l.kt, l.taps, l.c_in, l.c_out, t_in, src, l.c_out,
+                           t_alloc, t_off)
+            r = _FwdLayer(l, d, _lib.make_levels(shapes, B, l.t_out), src, wp, bias,
+                          torch.empty((L, _CF_ROWS, l.c_out), dtype=torch.float32, device=dev))
+            if prev is not None:
+                r.prev, r.s, r.fresh = prev, s, torch.empty((B * s * pix, l.c_out), dtype=tdt, device=dev)
             if train:
-                if min(lv.m[i] for i in range(L)) <= 1:
+                if min(r.lv.m[i] for i in range(L)) <= 1:
                     raise ValueError('Expected more than 1 value per channel when training, got input size %s'
                                      % str([B, l.c_out, l.t_out] + list(shapes[-1])))
-                w['rows_pl'] = (ctypes.c_int * _lib.MAX_LEVELS)()
-                if 'prev' in w:
-                    rows = lib.sfvos_shift_frames_stat_rows(ctypes.byref(pyr), B, l.t_out, l.c_out, w['rows_pl'])
+                r.rows_pl = (ctypes.c_int * _lib.MAX_LEVELS)()
+                if prev is not None:
+                    what, rows = 'sfvos_shift_frames_stat_rows', \
+                        lib.sfvos_shift_frames_stat_rows(ctypes.byref(pyr), B, l.t_out, l.c_out, r.rows_pl)
                 else:
-                    rows = lib.sfvos_conv3d_stat_rows(ctypes.byref(d), w['rows_pl'])
+                    what, rows = 'sfvos_conv3d_stat_rows', lib.sfvos_conv3d_stat_rows(ctypes.byref(d), r.rows_pl)
                 if rows <= 0:
-                    _lib.check(rows if rows < 0 else -1, 'sfvos_shift_frames_stat_rows' if 'prev' in w
-                               else 'sfvos_conv3d_stat_rows')
-                w['rows'] = rows
-                w['part'] = torch.empty((rows, 2, l.c_out), dtype=torch.float32, device=dev)
-            work[l.name] = w
+                    _lib.check(rows if rows < 0 else -1, what)
+                r.part = torch.empty((rows, 2, l.c_out), dtype=torch.float32, device=dev)
+            work.append(r)
         merged = [torch.empty((B, 256, H, W), dtype=torch.float32, device=dev) for (H, W) in shapes]
 
-        # -- phase 2: launches
+        # -- phase 2: launches.  Per layer: conv (of the s new frames only when reusing: the shift writes raw and,
+        # training, the statistics rows), BatchNorm statistics (batch or running), BN-apply (+ ReLU)
         if side is not None:
             side.wait_stream(main)
         ev = {}
-        coef = {}
-        order = list(plan.layers)
+        order = list(work)
         if side is not None and self.f1_alone:
             # fast_conv1's forward (57 % of the forward's time, one workgroup per CU) first and ALONE: the side stream
             # starts behind it.  Interleaving slow_conv1's workgroups with it buys nothing (both fill every CU) and the
             # slow pathway then overlaps the short fast_conv2/3 + BN launches, whose tails it fills.
-            order.sort(key=lambda l: l.name != 'f1')
-        for l in order:
-            conv, bn = getattr(self, l.conv), getattr(self, l.bn)
-            w = work[l.name]
-            d, lv, src, wp, cf = w['d'], w['lv'], w['src'], w['wp'], w['cf']
+            order.sort(key=lambda r: r.l.name != 'f1')
+        for r in order:
+            l, cf = r.l, r.cf
+            bn = getattr(self, l.bn)
             raw, dst = bufs[l.raw], bufs[l.dst]
             cs = _CF_ROWS * l.c_out
-            bias = _ptr(conv.bias.detach()) if conv.bias is not None else None
-            if 'bias8' in w:
-                bias = _ptr(w['bias8'])
             stream = side if (side is not None and self._on_side(l)) else main
             with torch.cuda.stream(stream):
                 st = _stream()
@@ -520,25 +545,22 @@ class SlowFastLayers(nn.Module):
                         stream.wait_event(ev['f1'])
                     if l.name == 'l2' and 'f2' in ev:
                         stream.wait_event(ev['f2'])
-                run = None   # running-statistics update of this layer (training), folded into its BN-apply launch
-                if 'prev' in w:   # reuse: s new frames, then the shift writes raw (and, training, the statistics rows)
-                    with self._t('conv_fwd', l.name):
-                        _lib.call('sfvos_conv3d', ctypes.byref(d), _ptr(src), _ptr(wp), bias, _ptr(w['fresh']), None,
-                                  st)
+                with self._t('conv_fwd', l.name):
+                    _lib.call('sfvos_conv3d', ctypes.byref(r.d), _ptr(r.src), _ptr(r.wp), r.bias,
+                              _ptr(raw if r.prev is None else r.fresh),
+                              _ptr(r.part) if train and r.prev is None else None, st)
+                if r.prev is not None:
                     with self._t('shift', l.name):
-                        _lib.call('sfvos_shift_frames', _ptr(w['prev']), _ptr(w['fresh']), _ptr(raw), dt_id,
-                                  ctypes.byref(pyr), B, l.t_out, w['s'], l.c_out, l.c_out,
-                                  _ptr(w['part']) if train else None, st)
+                        _lib.call('sfvos_shift_frames', _ptr(r.prev), _ptr(r.fresh), _ptr(raw), dt_id,
+                                  ctypes.byref(pyr), B, l.t_out, r.s, l.c_out, l.c_out,
+                                  _ptr(r.part) if train else None, st)
+                run = None   # running-statistics update of this layer (training), folded into its BN-apply launch
                 if train:
-                    if 'prev' not in w:
-                        with self._t('conv_fwd', l.name):
-                            _lib.call('sfvos_conv3d', ctypes.byref(d), _ptr(src), _ptr(wp), bias, _ptr(raw),
-                                      _ptr(w['part']), st)
                     if side is not None and self.f1_alone and l.name == 'f1':
                         e0 = torch.cuda.Event()
                         e0.record(stream)
                         side.wait_event(e0)
-                    _lib.call('sfvos_bn_finalize', _ptr(w['part']), L, w['rows_pl'], lv.m, _ptr(bn.weight.detach()),
+                    _lib.call('sfvos_bn_finalize', _ptr(r.part), L, r.rows_pl, r.lv.m, _ptr(bn.weight.detach()),
                               _ptr(bn.bias.detach()), float(bn.eps), l.c_out, _ptr(cf[0, _MEAN]), _ptr(cf[0, _RSTD]),
                               _ptr(cf[0, _SCALE]), _ptr(cf[0, _SHIFT]), _ptr(cf[0, _VARU]), cs, st)
                     if bn.track_running_stats and bn.running_mean is not None:
@@ -553,27 +575,19 @@ class SlowFastLayers(nn.Module):
                         run.n_updates, run.momentum = L, float(bn.momentum)
                         run = ctypes.byref(run)
                 else:
-                    if 'prev' not in w:
-                        with self._t('conv_fwd', l.name):
-                            _lib.call('sfvos_conv3d', ctypes.byref(d), _ptr(src), _ptr(wp), bias, _ptr(raw), None, st)
-                    _lib.call('sfvos_bn_eval_coeffs', _ptr(bn.weight.detach()), _ptr(bn.bias.detach()),
-                              _ptr(bn.running_mean), _ptr(bn.running_var), float(bn.eps), l.c_out, _ptr(cf[0, _MEAN]),
-                              _ptr(cf[0, _RSTD]), _ptr(cf[0, _SCALE]), _ptr(cf[0, _SHIFT]), st)
-                    if L > 1:
-                        cf[1:, :4] = cf[0, :4]  # same running statistics for every level (plumbing copy)
+                    _bn_eval_coeffs(bn, cf, st)
                 with self._t('bn_apply', l.name):
                     if l.dst in fp8_bufs:
                         _lib.call('sfvos_bn_apply_fp8', _ptr(raw), l.c_out, _ptr(dst, l.dst_off), dst.shape[-1],
-                                  ctypes.byref(lv), l.c_out, _ptr(cf[0, _SCALE]), _ptr(cf[0, _SHIFT]), cs,
+                                  ctypes.byref(r.lv), l.c_out, _ptr(cf[0, _SCALE]), _ptr(cf[0, _SHIFT]), cs,
                                   1 if l.relu else 0, float(self.fp8_act_scale), _ptr(self._fp8_sat), run, st)
                     else:
                         _lib.call('sfvos_bn_apply', _ptr(raw), l.c_out, _ptr(dst, l.dst_off), dst.shape[-1], dt_id,
-                                  ctypes.byref(lv), l.c_out, _ptr(cf[0, _SCALE]), _ptr(cf[0, _SHIFT]), cs,
+                                  ctypes.byref(r.lv), l.c_out, _ptr(cf[0, _SCALE]), _ptr(cf[0, _SHIFT]), cs,
                                   1 if l.relu else 0, run, st)
                 if side is not None and l.name in ('f1', 'f2'):
                     ev[l.name] = torch.cuda.Event()
                     ev[l.name].record(stream)
-            coef[l.name] = cf
         if side is not None:
             main.wait_stream(side)
 
@@ -587,7 +601,7 @@ class SlowFastLayers(nn.Module):
         if not keep:
             return merged, None
         state = _State()
-        state.B, state.shapes, state.bufs, state.coef = B, shapes, bufs, coef
+        state.B, state.shapes, state.bufs, state.coef = B, shapes, bufs, {r.l.name: r.cf for r in work}
         state.train, state.dtype_name, state.slow_offset = train, dt_name, slow_offset
         state.x_frames, state.x_pad = x_frames, x_pad
         del bufs['out']
@@ -647,9 +661,8 @@ class SlowFastLayers(nn.Module):
                 return torch.empty(shape, dtype=torch.float32, device=dev)
             direct.add(pname)
             return t
-        todo = []
+        todo = []   # holds every workspace until the streams are joined: nothing is released earlier
         written = set()
-        keepalive = []
         for l in reversed(plan.layers):
             conv = getattr(self, l.conv)
             first = l.src in ('xs0', 'xf0')
@@ -663,34 +676,32 @@ class SlowFastLayers(nn.Module):
                 continue
             lv = _lib.make_levels(shapes, B, l.t_out)
             rows = lib.sfvos_bn_bwd_rows(ctypes.byref(lv))
-            w = dict(l=l, lv=lv, rows=rows, need_in=need_in, need_w=need_w, need_b=need_b,
-                     part=torch.empty((rows, 2, l.c_out), dtype=torch.float32, device=dev),
-                     # dgamma and dbeta leave one kernel with one accumulate flag: both direct or neither
-                     dgamma=gout(l.bn + '.weight', (l.c_out,), sink_view(l.bn + '.bias') is not None),
-                     dbeta=gout(l.bn + '.bias', (l.c_out,), sink_view(l.bn + '.weight') is not None),
-                     dx=torch.empty((_lv_total(lv), l.c_out), dtype=tdt, device=dev))
-            if need_b:
-                w['bpart'] = torch.empty((rows, l.c_out), dtype=torch.float32, device=dev)
-                w['db'] = gout(l.conv + '.bias', (l.c_out,))
             sname, t_alloc, t_off = self._src_window(l, state.slow_offset, state.x_frames, state.x_pad)
-            w['src'] = bufs[sname]
+            r = _BwdLayer(l, lv, rows, need_in, need_w, need_b,
+                          torch.empty((rows, 2, l.c_out), dtype=torch.float32, device=dev),
+                          # dgamma and dbeta leave one kernel with one accumulate flag: both direct or neither
+                          gout(l.bn + '.weight', (l.c_out,), sink_view(l.bn + '.bias') is not None),
+                          gout(l.bn + '.bias', (l.c_out,), sink_view(l.bn + '.weight') is not None),
+                          torch.empty((_lv_total(lv), l.c_out), dtype=tdt, device=dev), bufs[sname])
+            if need_b:
+                r.bpart = torch.empty((rows, l.c_out), dtype=torch.float32, device=dev)
+                r.db = gout(l.conv + '.bias', (l.c_out,))
             if need_w:
-                d = self._desc(l, B, pyr, dt_id, w['src'], l.c_out, t_alloc, t_off)
-                nbytes = lib.sfvos_conv3d_wgrad_workspace_bytes(ctypes.byref(d))
+                r.wd = _conv_desc(dt_id, B, pyr, l.kt, l.taps, l.c_in, l.c_out, l.t_in, r.src, l.c_out, t_alloc, t_off)
+                nbytes = lib.sfvos_conv3d_wgrad_workspace_bytes(ctypes.byref(r.wd))
                 if nbytes == 0:
                     _lib.check(-1, 'sfvos_conv3d_wgrad_workspace_bytes')
-                w['wd'] = d
-                w['ws'] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                w['gw'] = gout(l.conv + '.weight', tuple(conv.weight.shape))
+                r.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                r.gw = gout(l.conv + '.weight', tuple(conv.weight.shape))
             if need_in:
                 if l.src not in gb:
                     galloc(l.src)
-                w['acc'] = 1 if l.src in written else 0
+                # conv over dy producing dx: channels swapped, full temporal padding
+                r.dd = _conv_desc(dt_id, B, pyr, l.kt, l.taps, l.c_out, l.c_in, l.t_out, l.c_out, gb[l.src].shape[-1],
+                                  pad_t=l.kt - 1, accumulate=1 if l.src in written else 0)
                 written.add(l.src)
-                w['dd'] = self._desc(l, B, pyr, dt_id, l.c_out, gb[l.src].shape[-1], dgrad=True, accumulate=w['acc'])
-                w['wpd'] = self._packed(l, 'dgrad', dt_name)
-            todo.append(w)
-            keepalive.append(w)
+                r.wpd = self._packed(l, 'dgrad', dt_name)
+            todo.append(r)
 
         # -- phase 2: launches.  Cross-pathway hand-offs: the fast side's data-gradient writes g(y_f2)/g(y_f1)
         # before the lateral's accumulates into it, and the next fast layer waits for that accumulate.
@@ -699,52 +710,49 @@ class SlowFastLayers(nn.Module):
         ev = {}
         wait_for = {'l2': 'f3', 'f2': 'l2', 'l1': 'f2', 'f1': 'l1'}
         grads = {}
-        for w in todo:
-            l = w['l']
+        for r in todo:
+            l, lv, dx = r.l, r.lv, r.dx
             conv, bn = getattr(self, l.conv), getattr(self, l.bn)
-            lv, rows = w['lv'], w['rows']
             cf = coef[l.name]
             cs = _CF_ROWS * l.c_out
             dy = gb[l.dst]
             raw = bufs[l.raw]
-            dx = w['dx']
             stream = side if (side is not None and self._on_side(l)) else main
             with torch.cuda.stream(stream):
                 st = _stream()
                 dep = wait_for.get(l.name)
                 if side is not None and dep in ev:
                     stream.wait_event(ev[dep])
-                treg = self._t('bn_bwd', l.name)
-                treg.__enter__()
-                _lib.call('sfvos_bn_bwd_reduce', _ptr(dy, l.dst_off), dy.shape[-1], _ptr(raw), l.c_out, dt_id,
-                          ctypes.byref(lv), l.c_out, _ptr(cf[0, _SCALE]), _ptr(cf[0, _SHIFT]), _ptr(cf[0, _MEAN]),
-                          _ptr(cf[0, _RSTD]), cs, 1 if l.relu else 0, _ptr(w['part']), st)
-                _lib.call('sfvos_bn_bwd_finalize', _ptr(w['part']), ctypes.byref(lv), _ptr(bn.weight.detach()),
-                          _ptr(cf[0, _MEAN]), _ptr(cf[0, _RSTD]), cs, l.c_out, 1 if state.train else 0,
-                          _ptr(cf[0, _CA]), _ptr(cf[0, _CB]), _ptr(cf[0, _CK]), _ptr(cf[0, _SDZ]), _ptr(cf[0, _SDZX]), st)
-                grads[l.bn + '.weight'], grads[l.bn + '.bias'] = w['dgamma'], w['dbeta']
-                _lib.call('sfvos_bn_bwd_apply', _ptr(dy, l.dst_off), dy.shape[-1], _ptr(raw), l.c_out, _ptr(dx),
-                          l.c_out, dt_id, ctypes.byref(lv), l.c_out, _ptr(cf[0, _SCALE]), _ptr(cf[0, _SHIFT]), cs,
-                          1 if l.relu else 0, _ptr(cf[0, _CA]), _ptr(cf[0, _CB]), _ptr(cf[0, _CK]),
-                          _ptr(w['bpart']) if w['need_b'] else None, _ptr(cf[0, _SDZ]), _ptr(cf[0, _SDZX]),
-                          _ptr(w['dgamma']), _ptr(w['dbeta']), sacc if (l.bn + '.weight') in direct else 0, st)
-                treg.__exit__(None, None, None)
-                if w['need_b']:
-                    _lib.call('sfvos_reduce_rows', _ptr(w['bpart']), rows, l.c_out, _ptr(w['db']),
+                with self._t('bn_bwd', l.name):
+                    _lib.call('sfvos_bn_bwd_reduce', _ptr(dy, l.dst_off), dy.shape[-1], _ptr(raw), l.c_out, dt_id,
+                              ctypes.byref(lv), l.c_out, _ptr(cf[0, _SCALE]), _ptr(cf[0, _SHIFT]), _ptr(cf[0, _MEAN]),
+                              _ptr(cf[0, _RSTD]), cs, 1 if l.relu else 0, _ptr(r.part), st)
+                    _lib.call('sfvos_bn_bwd_finalize', _ptr(r.part), ctypes.byref(lv), _ptr(bn.weight.detach()),
+                              _ptr(cf[0, _MEAN]), _ptr(cf[0, _RSTD]), cs, l.c_out, 1 if state.train else 0,
+                              _ptr(cf[0, _CA]), _ptr(cf[0, _CB]), _ptr(cf[0, _CK]), _ptr(cf[0, _SDZ]),
+                              _ptr(cf[0, _SDZX]), st)
+                    _lib.call('sfvos_bn_bwd_apply', _ptr(dy, l.dst_off), dy.shape[-1], _ptr(raw), l.c_out, _ptr(dx),
+                              l.c_out, dt_id, ctypes.byref(lv), l.c_out, _ptr(cf[0, _SCALE]), _ptr(cf[0, _SHIFT]), cs,
+                              1 if l.relu else 0, _ptr(cf[0, _CA]), _ptr(cf[0, _CB]), _ptr(cf[0, _CK]),
+                              _ptr(r.bpart) if r.need_b else None, _ptr(cf[0, _SDZ]), _ptr(cf[0, _SDZX]),
+                              _ptr(r.dgamma), _ptr(r.dbeta), sacc if (l.bn + '.weight') in direct else 0, st)
+                grads[l.bn + '.weight'], grads[l.bn + '.bias'] = r.dgamma, r.dbeta
+                if r.need_b:
+                    _lib.call('sfvos_reduce_rows', _ptr(r.bpart), r.rows, l.c_out, _ptr(r.db),
                               sacc if (l.conv + '.bias') in direct else 0, st)
-                    grads[l.conv + '.bias'] = w['db']
-                if w['need_in']:  # data gradient first: the other pathway may be waiting for it
+                    grads[l.conv + '.bias'] = r.db
+                if r.need_in:  # data gradient first: the other pathway may be waiting for it
                     with self._t('conv_dgrad', l.name):
-                        _lib.call('sfvos_conv3d', ctypes.byref(w['dd']), _ptr(dx), _ptr(w['wpd']), None,
-                                  _ptr(gb[l.src]), None, st)
+                        _lib.call('sfvos_conv3d', ctypes.byref(r.dd), _ptr(dx), _ptr(r.wpd), None, _ptr(gb[l.src]),
+                                  None, st)
                     if side is not None:
                         ev[l.name] = torch.cuda.Event()
                         ev[l.name].record(stream)
-                if w['need_w']:
+                if r.need_w:
                     with self._t('wgrad', l.name):
-                        _lib.call('sfvos_conv3d_wgrad', ctypes.byref(w['wd']), _ptr(w['src']), _ptr(dx), _ptr(w['gw']),
-                                  sacc if (l.conv + '.weight') in direct else 0, _ptr(w['ws']), st)
-                    grads[l.conv + '.weight'] = w['gw']
+                        _lib.call('sfvos_conv3d_wgrad', ctypes.byref(r.wd), _ptr(r.src), _ptr(dx), _ptr(r.gw),
+                                  sacc if (l.conv + '.weight') in direct else 0, _ptr(r.ws), st)
+                    grads[l.conv + '.weight'] = r.gw
                 if sink is not None:  # this layer's slice of the flat gradient is complete: exchange may start
                     done = [q for q in list(conv.parameters()) + list(bn.parameters())]
                     if all((n_ in direct) for n_ in ([l.conv + '.weight', l.bn + '.weight', l.bn + '.bias']
@@ -752,7 +760,6 @@ class SlowFastLayers(nn.Module):
                         sink.layer_done(done, stream)
         if side is not None:
             main.wait_stream(side)
-        del keepalive  # workspaces are released only after the join
         for n in direct:  # already in the optimiser's buffer: nothing for autograd to accumulate
             grads[n] = None
         if sink is not None:
@@ -760,49 +767,39 @@ class SlowFastLayers(nn.Module):
         return grads, gb
 
     # ------------------------------------------------------------------ input layout
-    def _to_pyramid(self, tensors, frames, dt_id, tdt):
-        """list over levels of [B,C,T,H,W] fp32 (any strides) -> flat pyramid buffer (model.py:157-158)."""
+    def _to_pyramid(self, tensors, frames, fp8=False):
+        """list over levels of [B,C,T,H,W] fp32 (any strides) -> flat pyramid buffer (model.py:157-158) in the compute
+        dtype, or with fp8 the e4m3 clip [C/64][M][64] (quantised with fp8_input_scale, saturation counted)."""
         B, C = tensors[0].shape[0], tensors[0].shape[1]
+        dev = tensors[0].device
         pix = sum(t.shape[3] * t.shape[4] for t in tensors)
         M = B * frames * pix
+        dt_id, tdt = _DT[self.precision]
         # bf16: channel-group-major ([C/32][M][32], see PackedClip) -- the layout the first convs read fastest
         grouped = tdt == torch.bfloat16 and C % 32 == 0 and os.environ.get('SFVOS_INPUT_LAYOUT', 'grouped') != 'ndhwc'
-        flat = torch.empty((C // 32, M, 32) if grouped else (M, C), dtype=tdt, device=tensors[0].device)
+        if fp8:
+            if C % 64 != 0:
+                raise RuntimeError("precision='fp8' needs an input channel count that is a multiple of 64")
+            flat = torch.empty((C // 64, M, 64), dtype=torch.uint8, device=dev)
+            if self._fp8_sat is None or self._fp8_sat.device != dev:
+                self._fp8_sat = torch.zeros(1, dtype=torch.int32, device=dev)
+        else:
+            flat = torch.empty((C // 32, M, 32) if grouped else (M, C), dtype=tdt, device=dev)
         st = _stream()
         off = 0
         for t in tensors:
             s = t if t.dtype == torch.float32 else t.float()
             H, W = s.shape[3], s.shape[4]
             for b in range(B):
+                frm = (_ptr(s[b]), s.stride(2), s.stride(1), s.stride(3), s.stride(4))
                 pos = off + b * frames * H * W
-                if grouped:
-                    _lib.call('sfvos_frames_to_groups', _ptr(s[b]), s.stride(2), s.stride(1), s.stride(3), s.stride(4),
-                              _ptr(flat, pos * 32), dt_id, frames, C, H, W, M * 32, st)
+                if fp8:
+                    _lib.call('sfvos_frames_to_groups_fp8', *frm, _ptr(flat, pos * 64), frames, C, H, W, M * 64,
+                              float(self.fp8_input_scale), _ptr(self._fp8_sat), st)
+                elif grouped:
+                    _lib.call('sfvos_frames_to_groups', *frm, _ptr(flat, pos * 32), dt_id, frames, C, H, W, M * 32, st)
                 else:
-                    _lib.call('sfvos_frames_to_ndhwc', _ptr(s[b]), s.stride(2), s.stride(1), s.stride(3), s.stride(4),
-                              _ptr(flat, pos * C), dt_id, frames, C, H, W, C, st)
-            off += B * frames * H * W
-        return flat
-
-    def _to_pyramid_fp8(self, tensors, frames):
-        """list over levels of [B,C,T,H,W] fp32 -> e4m3 clip [C/64][M][64] (sfvos_frames_to_groups_fp8)."""
-        B, C = tensors[0].shape[0], tensors[0].shape[1]
-        if C % 64 != 0:
-            raise RuntimeError("precision='fp8' needs an input channel count that is a multiple of 64")
-        pix = sum(t.shape[3] * t.shape[4] for t in tensors)
-        M = B * frames * pix
-        flat = torch.empty((C // 64, M, 64), dtype=torch.uint8, device=tensors[0].device)
-        if self._fp8_sat is None or self._fp8_sat.device != flat.device:
-            self._fp8_sat = torch.zeros(1, dtype=torch.int32, device=flat.device)
-        st = _stream()
-        off = 0
-        for t in tensors:
-            s = t if t.dtype == torch.float32 else t.float()
-            H, W = s.shape[3], s.shape[4]
-            for b in range(B):
-                _lib.call('sfvos_frames_to_groups_fp8', _ptr(s[b]), s.stride(2), s.stride(1), s.stride(3), s.stride(4),
-                          _ptr(flat, (off + b * frames * H * W) * 64), frames, C, H, W, M * 64,
-                          float(self.fp8_input_scale), _ptr(self._fp8_sat), st)
+                    _lib.call('sfvos_frames_to_ndhwc', *frm, _ptr(flat, pos * C), dt_id, frames, C, H, W, C, st)
             off += B * frames * H * W
         return flat
 
@@ -839,12 +836,16 @@ class SlowFastLayers(nn.Module):
                 raise RuntimeError('slow and fast inputs disagree in batch or spatial size')
         if len(fast_list) > _lib.MAX_LEVELS:
             raise RuntimeError('at most %d pyramid levels per call, got %d' % (_lib.MAX_LEVELS, len(fast_list)))
-        names = [n for n, _ in self.named_parameters()]
-        params = [p for _, p in self.named_parameters()]
-        keep = torch.is_grad_enabled() and (any(t.requires_grad for t in list(slow_list) + list(fast_list))
-                                            or any(p.requires_grad for p in params))
-        meta = dict(mode='frames', L=len(fast_list), keep=keep)
-        return _SlowFastPyramidFn.apply(self, meta, names, *(list(slow_list) + list(fast_list) + params))
+        return self._enhance(list(slow_list) + list(fast_list), mode='frames', L=len(fast_list))
+
+    def _enhance(self, inputs, **meta):
+        """_SlowFastPyramidFn over the clip tensors `inputs` and every parameter; meta: what the Function needs besides
+        (mode, L, and for mode 'packed' the clip's geometry).  The forward keeps autograd state only when some input
+        or parameter requires grad."""
+        named = list(self.named_parameters())
+        params = [p for _, p in named]
+        meta['keep'] = torch.is_grad_enabled() and any(t.requires_grad for t in inputs + params)
+        return _SlowFastPyramidFn.apply(self, meta, [n for n, _ in named], *(inputs + params))
 
     def forward(self, slow, fast):
         """(slow [B,C,Ts,H,W], fast [B,C,Tf,H,W]) -> (slow [B,224,1,H,W], fast [B,32,1,H,W]) -- model.py:118-149."""
@@ -887,12 +888,8 @@ class SlowFastLayers(nn.Module):
             slow_offset = plan.fp // 2 - plan.sp // 2
         if slow_offset < 0 or slow_offset + plan.sp > plan.fp:
             raise RuntimeError('slow window [%d, %d) outside the fast clip' % (slow_offset, slow_offset + plan.sp))
-        names = [n for n, _ in self.named_parameters()]
-        params = [p for _, p in self.named_parameters()]
-        keep = torch.is_grad_enabled() and (clip.data.requires_grad or any(p.requires_grad for p in params))
-        meta = dict(mode='packed', L=len(clip.shapes), keep=keep, shapes=clip.shapes, B=clip.batch,
-                    slow_offset=slow_offset, x_frames=clip.frames, x_pad=clip.pad[0])
-        merged = _SlowFastPyramidFn.apply(self, meta, names, clip.data, *params)
+        merged = self._enhance([clip.data], mode='packed', L=len(clip.shapes), shapes=clip.shapes, B=clip.batch,
+                               slow_offset=slow_offset, x_frames=clip.frames, x_pad=clip.pad[0])
         return OrderedDict(zip(clip.keys, merged))
 
 
@@ -900,7 +897,6 @@ class _SlowFastPyramidFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module, meta, names, *tensors):
         L, keep = meta['L'], meta['keep']
-        dt_id, tdt = _DT[module.precision]
         if meta['mode'] == 'frames':
             slow_list = [t.detach() for t in tensors[:L]]
             fast_list = [t.detach() for t in tensors[L:2 * L]]
@@ -908,13 +904,10 @@ class _SlowFastPyramidFn(torch.autograd.Function):
             B = fast_list[0].shape[0]
             shapes = [tuple(f.shape[3:]) for f in fast_list]
             slow_offset = module._slow_alias_offset(slow_list, fast_list)
-            if module.precision == 'fp8':
-                # the fast clip as e4m3 64-channel groups, read by fast_conv1 and (its centre frames) by slow_conv1
-                xf0 = module._to_pyramid_fp8(fast_list, module.plan.fp)
-                xs0 = None if slow_offset is not None else module._to_pyramid_fp8(slow_list, module.plan.sp)
-            else:
-                xf0 = module._to_pyramid(fast_list, module.plan.fp, dt_id, tdt)
-                xs0 = None if slow_offset is not None else module._to_pyramid(slow_list, module.plan.sp, dt_id, tdt)
+            # fp8: the fast clip as e4m3 64-channel groups, read by fast_conv1 and (its centre frames) by slow_conv1
+            fp8 = module.precision == 'fp8'
+            xf0 = module._to_pyramid(fast_list, module.plan.fp, fp8)
+            xs0 = None if slow_offset is not None else module._to_pyramid(slow_list, module.plan.sp, fp8)
             ctx.in_meta = [(t.shape, t.dtype) for t in tensors[:n_in]]
         else:
             n_in = 1

@@ -6,15 +6,11 @@ The parameters stay ordinary nn.Parameters (the reference's `SGD(model.parameter
 keeps working on them); FusedSGD re-homes their storage into a flat buffer so that
   * the optimiser step is a single launch, and
   * the data-parallel gradient all-reduce is a single RCCL collective on the flat grad."""
-import ctypes
 
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+from .module import _ptr, _stream
 
 
 class FusedSGD(torch.optim.Optimizer):
@@ -176,7 +172,7 @@ class FusedSGD(torch.optim.Optimizer):
                     p.grad.data_ptr() >= self.flat_grad.data_ptr() + self.flat_grad.numel() * 4:
                 raise RuntimeError('FusedSGD: a parameter .grad was re-allocated outside the flat gradient buffer; '
                                    'use optimizer.zero_grad() (set_to_none=False)')
-        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        st = _stream()
         _lib.call('sfvos_sgd_step', _ptr(self.flat_param), _ptr(self.flat_grad), _ptr(self.flat_buf),
                   self.flat_param.numel(), float(g['lr']), float(g['momentum']), float(g['weight_decay']),
                   1 if self._steps == 0 else 0, st)

@@ -27,7 +27,7 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
-from .module import _CF_ROWS, _DT, _MEAN, _RSTD, _SCALE, _SHIFT, _ptr, _stream
+from .module import _CF_ROWS, _DT, _SCALE, _SHIFT, _bn_eval_coeffs, _conv_desc, _ptr, _stream
 
 
 class _Ring(object):
@@ -100,12 +100,8 @@ class SlowFastStream(object):
         weights are re-packed on demand by the module's own cache."""
         st = _stream()
         for l in self.plan.layers:
-            bn = getattr(self.m, l.bn)
-            cf = torch.empty((1, _CF_ROWS, l.c_out), dtype=torch.float32, device=self.dev)
-            _lib.call('sfvos_bn_eval_coeffs', _ptr(bn.weight.detach()), _ptr(bn.bias.detach()), _ptr(bn.running_mean),
-                      _ptr(bn.running_var), float(bn.eps), l.c_out, _ptr(cf[0, _MEAN]), _ptr(cf[0, _RSTD]),
-                      _ptr(cf[0, _SCALE]), _ptr(cf[0, _SHIFT]), st)
-            self.cf[l.name] = cf
+            self.cf[l.name] = torch.empty((1, _CF_ROWS, l.c_out), dtype=torch.float32, device=self.dev)
+            _bn_eval_coeffs(getattr(self.m, l.bn), self.cf[l.name], st)
 
     def reset(self):
         """Start a new sequence."""
@@ -151,16 +147,9 @@ class SlowFastStream(object):
         l = self.plan.layer(name)
         ring = self.rings[src]
         conv = getattr(self.m, l.conv)
-        d = _lib.ConvDesc()
-        d.dtype, d.batch, d.kt, d.taps, d.pyr = self.dt_id, 1, l.kt, l.taps, self.pyr
-        d.t_in, d.c_in, d.c_out, d.pad_t = l.kt + g - 1, l.c_in, l.c_out, 0
-        d.t_alloc, d.t_offset = 2 * ring.T, (o0 + src_shift) % ring.T
-        d.ld_y, d.accumulate = l.c_out, 0
+        d = _conv_desc(self.dt_id, 1, self.pyr, l.kt, l.taps, l.c_in, l.c_out, l.kt + g - 1, ring.buf, l.c_out,
+                       2 * ring.T, (o0 + src_shift) % ring.T)
         d.x_frame_stride = d.y_frame_stride = self.FS
-        if ring.grouped:
-            d.ld_x, d.x_group_stride = 32, ring.buf.shape[1] * 32
-        else:
-            d.ld_x, d.x_group_stride = ring.C, 0
         st = _stream()
         raw = self.raw[name]
         bias = _ptr(conv.bias.detach()) if conv.bias is not None else None

@@ -17,27 +17,18 @@ Every window is a view of the resident sequence: sfvos_conv_desc.t_alloc / t_off
 buffer, and the frames beyond the ends are zero frames that are never read -- no per-window copy of the input."""
 from collections import OrderedDict
 
-import torch
-
 from . import _lib
-from .module import _DT, RawReuse, _SlowFastPyramidFn
+from .module import _DT, RawReuse
 
 REUSED_LAYERS = ('f1', 's1')
 
 
-def weight_tag(conv):
-    """What identifies a conv's weights between two calls: (_version, data_ptr) of weight and bias, and the weight
-    epoch FusedSGD bumps (torch.optim.SGD.step and load_state_dict bump _version)."""
-    parts = [(p._version, p.data_ptr()) for p in (conv.weight, conv.bias) if p is not None]
-    return tuple(parts) + (_lib.weight_epoch(),)
-
-
 def window_tag(seq, conv, precision):
     """Everything a layer's pre-BN frames depend on besides the centre frame: the sequence (storage, _version,
-    pyramid), the precision and the weights."""
+    pyramid), the precision and the weights (_lib.weight_tag of weight and bias)."""
     d = seq.data
     return (d.untyped_storage().data_ptr(), d.storage_offset(), d._version, tuple(d.shape), d.dtype,
-            tuple(seq.shapes), precision, weight_tag(conv))
+            tuple(seq.shapes), precision, _lib.weight_tag((conv.weight, conv.bias)))
 
 
 def reuse_shift(prev_centre, centre, t_out, prev_tag, tag):
@@ -108,14 +99,10 @@ class SlowFastWindows(object):
             if s and n in self._raw:
                 prev[n] = (self._raw[n], s)
         hook = RawReuse(prev) if self.reuse else None
-        names = [n for n, _ in m.named_parameters()]
-        params = [p for _, p in m.named_parameters()]
-        keep = torch.is_grad_enabled() and any(p.requires_grad for p in params)
         # the window is frames [i - fp//2, i - fp//2 + fp) of the sequence; the slow pathway reads its centre frames
         # (enhance_packed's default slow_offset)
-        meta = dict(mode='packed', L=len(seq.shapes), keep=keep, shapes=seq.shapes, B=1,
-                    slow_offset=plan.fp // 2 - plan.sp // 2, x_frames=N, x_pad=plan.fp // 2 - i, reuse=hook)
-        merged = _SlowFastPyramidFn.apply(m, meta, names, seq.data, *params)
+        merged = m._enhance([seq.data], mode='packed', L=len(seq.shapes), shapes=seq.shapes, B=1,
+                            slow_offset=plan.fp // 2 - plan.sp // 2, x_frames=N, x_pad=plan.fp // 2 - i, reuse=hook)
         self.reused = {n: (plan.layer(n).t_out - prev[n][1]) if n in prev else 0 for n in REUSED_LAYERS}
         if hook is not None:
             self._centre, self._raw, self._tags = i, dict(hook.raw), tags
