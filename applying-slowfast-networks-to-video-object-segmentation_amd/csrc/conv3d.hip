@@ -1190,8 +1190,6 @@ struct ConvPlan {
 
 // Frame blocks: fewest blocks of at most max_tt frames, sizes as even as possible and NO padded frame:
 // rem blocks of base+1 frames (first launch) followed by nblk-rem blocks of base frames (second launch).
-static void split_frames(int t_out, int max_tt, ConvPlan* p);
-
 static void split_frames(int t_out, int max_tt, ConvPlan* p) {
   const int nblk = ceil_div(t_out, max_tt), base = t_out / nblk, rem = t_out % nblk;
   p->t_blocks = nblk;
@@ -1264,23 +1262,12 @@ static void split_frames_balanced(int t_out, long long units, ConvPlan* p) {
 }
 
 static int make_plan(const sfvos_conv_desc* d, ConvPlan* p) {
-  SFVOS_REQUIRE(d != nullptr, "conv: null desc");
+  if (int rc = check_conv_desc(d, "conv")) return rc;
   p->stat = 0;
-  SFVOS_REQUIRE(d->struct_size == (int)sizeof(sfvos_conv_desc),
-                "conv: sfvos_conv_desc.struct_size is %d, this library's struct has %d bytes (stale binding?)",
-                d->struct_size, (int)sizeof(sfvos_conv_desc));
-  SFVOS_REQUIRE(d->dtype == SFVOS_F32 || d->dtype == SFVOS_BF16 || d->dtype == SFVOS_FP8, "conv: bad dtype %d", d->dtype);
-  SFVOS_REQUIRE(d->taps == 9 || d->taps == 1, "conv: taps must be 9 or 1, got %d", d->taps);
-  SFVOS_REQUIRE(d->c_in > 0 && d->c_in % 32 == 0 && d->c_out > 0 && d->c_out % 32 == 0,
-                "conv: channels must be positive multiples of 32 (c_in %d, c_out %d)", d->c_in, d->c_out);
   SFVOS_REQUIRE(d->c_out <= 256, "conv: c_out %d > 256 unsupported", d->c_out);
-  SFVOS_REQUIRE(d->batch >= 1 && d->t_in >= 1 && d->kt >= 1, "conv: bad extent");
-  SFVOS_REQUIRE(d->t_alloc >= 1, "conv: t_alloc %d", d->t_alloc);
-  // level-major x: the window [t_offset, t_offset + t_in) may stick out of the buffer's t_alloc frames on either side;
-  // those frames are zeros (never read).  The frame-major ring is addressed modulo its slots by the caller: in range.
+  // the frame-major ring is addressed modulo its slots by the caller: the window is inside them
   SFVOS_REQUIRE(d->x_frame_stride == 0 || (d->t_offset >= 0 && d->t_alloc >= d->t_offset + d->t_in),
                 "conv: ring window [t_offset %d, +t_in %d) exceeds its %d slots", d->t_offset, d->t_in, d->t_alloc);
-  SFVOS_REQUIRE(d->t_offset > -(1 << 20) && d->t_offset < (1 << 20) && d->t_in < (1 << 20), "conv: window out of range");
   SFVOS_REQUIRE(d->pad_t >= 0 && d->pad_t < d->kt + 1, "conv: bad pad_t %d", d->pad_t);
   const int ce = d->dtype == SFVOS_BF16 ? 8 : d->dtype == SFVOS_FP8 ? 16 : 4;
   if (d->dtype == SFVOS_FP8)
@@ -1296,23 +1283,16 @@ static int make_plan(const sfvos_conv_desc* d, ConvPlan* p) {
     SFVOS_REQUIRE(d->ld_x >= d->c_in, "conv: pitch smaller than channel count");
     SFVOS_REQUIRE(d->ld_x % ce == 0, "conv: ld_x %d must be a multiple of %d (16-byte chunks)", d->ld_x, ce);
   }
-  SFVOS_REQUIRE(d->pyr.n_levels >= 1 && d->pyr.n_levels <= SFVOS_MAX_LEVELS, "conv: n_levels %d out of [1,%d]",
-                d->pyr.n_levels, SFVOS_MAX_LEVELS);
   p->t_out = d->t_in + 2 * d->pad_t - d->kt + 1;
   SFVOS_REQUIRE(p->t_out >= 1, "conv: kernel longer than padded input (t_in %d, kt %d, pad_t %d)", d->t_in, d->kt,
                 d->pad_t);
   constexpr int WNW = 2;  // waves across the channel dimension (mid / wide families)
-  bool lateral_ok = true;
-#ifdef SFVOS_DIAG
-  lateral_ok = !getenv("SFVOS_NO_LATERAL_KERNEL");
-#endif
-  if (lateral_ok && lateral_fwd_applies(d)) {
+  LevelTable t;
+  if (lateral_kernels_on() && lateral_fwd_applies(d)) {
     p->family = 4; split_frames(p->t_out, 3, p); p->MT = 1; p->NT = 1; p->TH = 8; p->BN = 64;
   } else if (d->c_out <= 32 && d->taps == 9) {
-    long long units = 0;
-    for (int l = 0; l < d->pyr.n_levels && l < SFVOS_MAX_LEVELS; ++l)
-      units += (long long)d->batch * ceil_div(d->pyr.h[l] > 0 ? d->pyr.h[l] : 1, 8) * ceil_div(d->pyr.w[l] > 0 ? d->pyr.w[l] : 1, 32);
-    p->family = 3; split_frames_balanced(p->t_out, units, p); p->NT = 1; p->TH = 8; p->BN = 32;
+    // units: the 8 x 32 pixel tiles of all levels and clips
+    p->family = 3; split_frames_balanced(p->t_out, level_table(d, 1, 1, 8, 32, &t), p); p->NT = 1; p->TH = 8; p->BN = 32;
     if (d->t_in == 1 && d->pad_t == d->kt - 1 && d->kt > 1 && d->dtype == SFVOS_BF16) {
       // data gradient of a conv with ONE output frame (fast_conv3): every frame of dx meets exactly one temporal tap, so
       // a multi-frame block multiplies TT taps x TT frames of which TT are real.  One workgroup per pixel tile keeps
@@ -1362,44 +1342,30 @@ static int make_plan(const sfvos_conv_desc* d, ConvPlan* p) {
     }
   }
   p->n_blocks = ceil_div(d->c_out, p->BN);
+  // frame-major ring: frame t of every level sits at position t * x_frame_stride (one frame per clip and level)
+  const bool xring = d->x_frame_stride > 0, yring = d->y_frame_stride > 0;
+  const long long rows = p->t_blocks * level_table(d, xring ? 1 : d->t_alloc, yring ? 1 : p->t_out, p->TH, 32, &t);
   ConvLevels& lv = p->lv;
-  lv.n = d->pyr.n_levels;
-  long long wg = 0, rows = 0, px = 0;
-  for (int l = 0; l < SFVOS_MAX_LEVELS; ++l) {
-    const bool live = l < lv.n;
-    const int H = live ? d->pyr.h[l] : 1, W = live ? d->pyr.w[l] : 1;
-    SFVOS_REQUIRE(H >= 1 && W >= 1, "conv: level %d has bad extent %dx%d", l, H, W);
-    SFVOS_REQUIRE((long long)H * W * (d->x_group_stride ? 4 * ce : d->ld_x) * (16 / ce) < (1ll << 31),
-                  "conv: level %d frame of %dx%d x pitch %d exceeds the 2 GiB per-frame offset range", l, H, W,
-                  d->ld_x);
-    lv.H[l] = H; lv.W[l] = W;
-    lv.tiles_h[l] = ceil_div(H, p->TH); lv.tiles_w[l] = ceil_div(W, 32);
-    lv.wg_begin[l] = (int)wg; lv.row_begin[l] = (int)rows;
-    if (d->x_frame_stride > 0) {  // frame-major ring: frame t of every level sits at position t * x_frame_stride
-      lv.xpos[l] = (long long)d->batch * px; lv.xbs[l] = (long long)H * W; lv.xfs[l] = d->x_frame_stride;
-    } else {
-      lv.xpos[l] = (long long)d->batch * d->t_alloc * px; lv.xbs[l] = (long long)d->t_alloc * H * W; lv.xfs[l] = (long long)H * W;
-    }
-    if (d->y_frame_stride > 0) {
-      lv.ypos[l] = (long long)d->batch * px; lv.ybs[l] = (long long)H * W; lv.yfs[l] = d->y_frame_stride;
-    } else {
-      lv.ypos[l] = (long long)d->batch * p->t_out * px; lv.ybs[l] = (long long)p->t_out * H * W; lv.yfs[l] = (long long)H * W;
-    }
-    if (live) {
-      // pixel tiles padded to groups of 8 (XCD-aware order in the kernel)
-      wg += (long long)d->batch * p->n_blocks * ceil_div(lv.tiles_h[l] * lv.tiles_w[l], 8) * 8;  // x blocks per launch
-      rows += (long long)d->batch * p->t_blocks * lv.tiles_h[l] * lv.tiles_w[l];
-      px += (long long)H * W;
-    }
-    SFVOS_REQUIRE(wg < (1ll << 31) && rows < (1ll << 31), "conv: grid out of range");
+  lv.n = t.n;
+  long long wg = 0;
+  for (int l = 0; l <= SFVOS_MAX_LEVELS; ++l) {
+    lv.wg_begin[l] = (int)wg; lv.row_begin[l] = (int)((long long)p->t_blocks * t.tile_begin[l]);
+    if (l == SFVOS_MAX_LEVELS) break;
+    const long long HW = (long long)t.H[l] * t.W[l];
+    lv.H[l] = t.H[l]; lv.W[l] = t.W[l]; lv.tiles_h[l] = t.tiles_h[l]; lv.tiles_w[l] = t.tiles_w[l];
+    lv.xpos[l] = t.xpos[l]; lv.ypos[l] = t.ypos[l];
+    // positions between consecutive clips / frames of the level
+    lv.xbs[l] = xring ? HW : d->t_alloc * HW; lv.xfs[l] = xring ? d->x_frame_stride : HW;
+    lv.ybs[l] = yring ? HW : p->t_out * HW; lv.yfs[l] = yring ? d->y_frame_stride : HW;
+    // pixel tiles padded to groups of 8 (XCD-aware order in the kernel): x blocks per launch
+    if (l < lv.n) wg += (long long)d->batch * p->n_blocks * ceil_div(t.tiles_h[l] * t.tiles_w[l], 8) * 8;
   }
-  lv.wg_begin[SFVOS_MAX_LEVELS] = (int)wg;
-  lv.row_begin[SFVOS_MAX_LEVELS] = (int)rows;
+  SFVOS_REQUIRE(wg < (1ll << 31) && rows < (1ll << 31), "conv: grid out of range");
   if (p->family == 4) {  // rows are the workgroups of the lateral kernel
-    rows = 0;
+    long long r = 0;
     for (int l = 0; l <= SFVOS_MAX_LEVELS; ++l) {
-      lv.row_begin[l] = (int)rows;
-      if (l < lv.n) rows += lateral_fwd_rows(d, l);
+      lv.row_begin[l] = (int)r;
+      if (l < lv.n) r += lateral_fwd_rows(d, l);
     }
   }
   return SFVOS_OK;
@@ -1408,45 +1374,19 @@ static int make_plan(const sfvos_conv_desc* d, ConvPlan* p) {
 template <int DT, int TAPS, int TPS, int TT, int MT, int NT, int WS, int WN, int CIN = 0>
 static int launch(const ConvArgs& a, long long grid, hipStream_t stream) {
   typedef ConvCfg<DT, TAPS, TPS, TT, MT, NT, WS, WN> C;
-  auto kern = conv3d_kernel<DT, TAPS, TPS, TT, MT, NT, WS, WN, CIN>;
-  static LdsAttrOnce once;
-  if (int rc = once.ensure((const void*)kern, C::LDS_BYTES, "conv")) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(C::NTHREADS), C::LDS_BYTES, stream, a);
-  return check_launch("conv3d");
-}
-
-template <int DT, int CIN = 0>
-static int launch_fs1s(const ConvArgs& a, long long grid, hipStream_t stream) {
-  if constexpr (DT == SFVOS_BF16) {
-    constexpr int LDS1 = FsCfg<DT, 1, 4>::LDS_BYTES;
-    auto kern = conv3d_fs1s_kernel<DT, CIN>;
-    static LdsAttrOnce once;
-    if (int rc = once.ensure((const void*)kern, LDS1, "conv")) return rc;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), LDS1, stream, a);
-    return check_launch("conv3d_fs1s");
-  } else {
-    set_error("conv: the input-stationary sweep is a bf16 kernel");
-    return SFVOS_E_ARG;
-  }
+  return launch_lds<conv3d_kernel<DT, TAPS, TPS, TT, MT, NT, WS, WN, CIN>>(dim3((unsigned)grid), dim3(C::NTHREADS),
+                                                                            C::LDS_BYTES, C::LDS_BYTES, stream, "conv3d", a);
 }
 
 template <int DT, int CIN = 0>
 static int launch_fs(const ConvArgs& a, long long grid, hipStream_t stream) {
   if constexpr (DT == SFVOS_BF16) if (a.part[0].wgs == 0 && a.part[1].wgs == 0) {  // single-frame blocks only
     constexpr int LDS1 = FsCfg<DT, 1, 4>::LDS_BYTES;
-    auto kern1 = conv3d_fs1_kernel<DT, CIN>;
-    static LdsAttrOnce once1;
-    if (int rc = once1.ensure((const void*)kern1, LDS1, "conv")) return rc;
-    hipLaunchKernelGGL(kern1, dim3((unsigned)grid), dim3(512), LDS1, stream, a);
-    return check_launch("conv3d_fs1");
+    return launch_lds<conv3d_fs1_kernel<DT, CIN>>(dim3((unsigned)grid), dim3(512), LDS1, LDS1, stream, "conv3d_fs1", a);
   }
   constexpr int LDS = FsCfg<DT, 4, 1>::LDS_BYTES;  // the largest of the three bodies
   static_assert(LDS >= FsCfg<DT, 2, 2>::LDS_BYTES && LDS >= FsCfg<DT, 1, 4>::LDS_BYTES, "LDS of the merged launch");
-  auto kern = conv3d_fs_kernel<DT, CIN>;
-  static LdsAttrOnce once;
-  if (int rc = once.ensure((const void*)kern, LDS, "conv")) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), LDS, stream, a);
-  return check_launch("conv3d_fs");
+  return launch_lds<conv3d_fs_kernel<DT, CIN>>(dim3((unsigned)grid), dim3(512), LDS, LDS, stream, "conv3d_fs", a);
 }
 
 template <int DT, int TAPS>
@@ -1501,12 +1441,8 @@ extern "C" int sfvos_conv3d(const sfvos_conv_desc* d, const void* x, const void*
   SFVOS_REQUIRE(d->ld_y % (d->dtype == SFVOS_F32 ? 4 : 8) == 0, "conv: ld_y %d must be a multiple of a 16-byte chunk", d->ld_y);
   SFVOS_REQUIRE(d->dtype != SFVOS_FP8 || bias != nullptr, "conv: e4m3 operands need the [2][c_out] (bias, descale) rows");
   SFVOS_REQUIRE(!(d->taps == 1 && p.family == 2), "conv: 1x1 conv with c_out > 64 has no kernel instance");
-  bool lateral_ok = true;
-#ifdef SFVOS_DIAG
-  lateral_ok = !getenv("SFVOS_NO_LATERAL_KERNEL");
-#endif
   if (!bias && !stat_part && d->taps == 1 && d->x_group_stride == 0 && d->x_frame_stride == 0 &&
-      d->y_frame_stride == 0 && !d->relu && lateral_ok) {
+      d->y_frame_stride == 0 && !d->relu && lateral_kernels_on()) {
     rc = lateral_dgrad_try(d, x, w_packed, y, (hipStream_t)stream);  // lateral data gradient: its own HBM-bound kernel
     if (rc >= 0) return rc;
   }
@@ -1545,7 +1481,10 @@ extern "C" int sfvos_conv3d(const sfvos_conv_desc* d, const void* x, const void*
       grid += wgs;
     }
     SFVOS_REQUIRE(grid > 0 && grid < (1ll << 31), "conv: grid %lld out of range", grid);
-    if (p.stat) return launch_fs1s<SFVOS_BF16>(a, grid, s);   // (make_plan sets it for bf16 only)
+    if (p.stat) {  // (make_plan sets it for bf16 only)
+      constexpr int LDS1 = FsCfg<SFVOS_BF16, 1, 4>::LDS_BYTES;
+      return launch_lds<conv3d_fs1s_kernel<SFVOS_BF16>>(dim3((unsigned)grid), dim3(512), LDS1, LDS1, s, "conv3d_fs1s", a);
+    }
     if (d->dtype == SFVOS_BF16)
       return d->c_in == 256 ? launch_fs<SFVOS_BF16, 256>(a, grid, s) : launch_fs<SFVOS_BF16>(a, grid, s);
     if (d->dtype == SFVOS_FP8) return d->c_in == 256 ? launch_fs<SFVOS_FP8, 256>(a, grid, s) : launch_fs<SFVOS_FP8>(a, grid, s);

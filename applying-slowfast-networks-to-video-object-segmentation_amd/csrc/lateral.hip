@@ -340,10 +340,11 @@ constexpr int LAT_FWD_MAX_KT = LAT_FWD_LDS_KT + 1;  // ... plus one tap in regis
 // waves per workgroup: 12 waves per compute unit as 3 x 4 (weights <= 52 KB), 2 x 6 (<= 80 KB) or 1 x 12
 static int lateral_fwd_nw(const sfvos_conv_desc* d) { return d->kt <= 13 ? 4 : d->kt <= 20 ? 6 : 12; }
 
-// The shapes the forward kernel covers (make_plan asks: the statistics rows are per workgroup of THIS kernel).
+// The shapes the forward kernel covers (make_plan asks, after check_conv_desc: the statistics rows are per workgroup of
+// THIS kernel).
 bool lateral_fwd_applies(const sfvos_conv_desc* d) {
   const int t_out = d->t_in - d->kt + 1;
-  return d->dtype == SFVOS_BF16 && d->taps == 1 && d->c_in == 32 && d->c_out == 64 && d->pad_t == 0 && d->kt >= 1 &&
+  return d->dtype == SFVOS_BF16 && d->taps == 1 && d->c_in == 32 && d->c_out == 64 && d->pad_t == 0 &&
          d->kt <= LAT_FWD_MAX_KT && t_out >= 1 && t_out <= 3 && d->accumulate == 0 && d->x_group_stride == 0 &&
          d->x_frame_stride == 0 && d->y_frame_stride == 0 && d->t_offset >= 0 && d->t_offset + d->t_in <= d->t_alloc &&
          d->ld_x % 8 == 0 && d->ld_y % 4 == 0;
@@ -360,35 +361,24 @@ int lateral_fwd_launch(const sfvos_conv_desc* d, const void* x, const void* w_pa
   a.x = (const char*)x; a.wp = (const char*)w_packed; a.bias = bias; a.y = (char*)y; a.stat_part = stat_part;
   a.t_in = d->t_in; a.t_alloc = d->t_alloc; a.t_offset = d->t_offset; a.t_out = d->t_in - d->kt + 1; a.kt = d->kt;
   a.ld_x = d->ld_x; a.ld_y = d->ld_y; a.batch = d->batch; a.relu = d->relu;
-  a.n = d->pyr.n_levels;
-  long long wg = 0, px = 0;
-  for (int l = 0; l < SFVOS_MAX_LEVELS; ++l) {
-    const bool live = l < a.n;
-    const int HW = live ? d->pyr.h[l] * d->pyr.w[l] : 1;
-    a.HW[l] = HW;
+  LevelTable t;
+  level_table(d, d->t_alloc, a.t_out, 0, 32, &t);
+  copy_levels_1d(t, &a.n, a.HW, a.wg_begin, a.xpos, a.ypos);
+  long long wg = 0;  // a workgroup takes nw of the level's 32-position tiles
+  for (int l = 0; l <= SFVOS_MAX_LEVELS; ++l) {
     a.wg_begin[l] = (int)wg;
-    a.xpos[l] = (long long)d->batch * a.t_alloc * px;
-    a.ypos[l] = (long long)d->batch * a.t_out * px;
-    if (live) {
-      wg += lateral_fwd_rows(d, l);
-      px += HW;
-    }
+    if (l < a.n) wg += lateral_fwd_rows(d, l);
   }
-  a.wg_begin[SFVOS_MAX_LEVELS] = (int)wg;
   SFVOS_REQUIRE(wg > 0 && wg < (1ll << 30), "conv: grid out of range");
   const int nw = lateral_fwd_nw(d);
   const bool wreg = a.kt > LAT_FWD_LDS_KT;
   const int kl = wreg ? a.kt - 1 : a.kt;
   const int lds = kl * 4096 > nw * 512 ? kl * 4096 : nw * 512;
   const dim3 grid((unsigned)wg);
-#define SFVOS_LATF(TOUTv, NWv, WREGv)                                                                       \
-  if (a.t_out == TOUTv && nw == NWv && wreg == WREGv) {                                                     \
-    auto kern = lateral_fwd_kernel<TOUTv, NWv, WREGv>;                                                      \
-    static LdsAttrOnce once;                                                                                \
-    if (int rc = once.ensure((const void*)kern, LAT_FWD_LDS_KT * 4096, "lateral_fwd")) return rc;           \
-    hipLaunchKernelGGL(kern, grid, dim3(64 * NWv), lds, stream, a);                                         \
-    return check_launch("lateral_fwd");                                                                     \
-  }
+#define SFVOS_LATF(TOUTv, NWv, WREGv)                                                                               \
+  if (a.t_out == TOUTv && nw == NWv && wreg == WREGv)                                                               \
+    return launch_lds<lateral_fwd_kernel<TOUTv, NWv, WREGv>>(grid, dim3(64 * NWv), lds, LAT_FWD_LDS_KT * 4096, stream, \
+                                                             "lateral_fwd", a);
   SFVOS_LATF(1, 4, false) SFVOS_LATF(2, 4, false) SFVOS_LATF(3, 4, false)
   SFVOS_LATF(1, 6, false) SFVOS_LATF(2, 6, false) SFVOS_LATF(3, 6, false)
   SFVOS_LATF(1, 12, false) SFVOS_LATF(2, 12, false) SFVOS_LATF(3, 12, false)
@@ -397,32 +387,20 @@ int lateral_fwd_launch(const sfvos_conv_desc* d, const void* x, const void* w_pa
   return SFVOS_E_ARG;
 }
 
-// Called by sfvos_conv3d for the shapes this kernel covers; returns -1 when it does not apply.
+// Called by sfvos_conv3d (after make_plan) for the shapes this kernel covers; returns -1 when it does not apply.
 int lateral_dgrad_try(const sfvos_conv_desc* d, const void* x, const void* w_packed, void* y, hipStream_t stream) {
-  if (!(d->dtype == SFVOS_BF16 && d->taps == 1 && d->c_out == 32 && d->kt >= 1 && d->pad_t == d->kt - 1 &&
-        (d->c_in == 32 || d->c_in == 64) && d->t_in >= 1 && d->t_in <= 3 && d->t_offset == 0 && d->t_alloc == d->t_in &&
+  if (!(d->dtype == SFVOS_BF16 && d->taps == 1 && d->c_out == 32 && d->pad_t == d->kt - 1 &&
+        (d->c_in == 32 || d->c_in == 64) && d->t_in <= 3 && d->t_offset == 0 && d->t_alloc == d->t_in &&
         d->ld_x % 8 == 0 && d->ld_y % 4 == 0))
     return -1;
   LatArgs a;
   a.dy = (const char*)x; a.wp = (const char*)w_packed; a.dx = (char*)y;
   a.t_in = d->t_in; a.t_out = d->t_in + d->kt - 1; a.kt = d->kt; a.ld_dy = d->ld_x; a.ld_dx = d->ld_y;
   a.accumulate = d->accumulate; a.batch = d->batch;
-  a.lv.n = d->pyr.n_levels;
-  long long waves = 0, px = 0;
-  for (int l = 0; l < SFVOS_MAX_LEVELS; ++l) {
-    const bool live = l < a.lv.n;
-    const int HW = live ? d->pyr.h[l] * d->pyr.w[l] : 1;
-    a.lv.HW[l] = HW;
-    a.lv.wave_begin[l] = (int)waves;
-    a.lv.xpos[l] = (long long)d->batch * a.t_in * px;
-    a.lv.ypos[l] = (long long)d->batch * a.t_out * px;
-    if (live) {
-      waves += (long long)d->batch * ceil_div(HW, 32);
-      px += HW;
-    }
-  }
-  a.lv.wave_begin[SFVOS_MAX_LEVELS] = (int)waves;
-  if (waves <= 0 || waves >= (1ll << 30)) return -1;
+  LevelTable t;
+  const long long waves = level_table(d, a.t_in, a.t_out, 0, 32, &t);
+  if (waves >= (1ll << 30)) return -1;
+  copy_levels_1d(t, &a.lv.n, a.lv.HW, a.lv.wave_begin, a.lv.xpos, a.lv.ypos);
   a.n_waves = (int)waves;
   const int ks = d->c_in / 32;
   const int image = ks * d->kt * 2048;  // the packed data-gradient image
@@ -436,14 +414,10 @@ int lateral_dgrad_try(const sfvos_conv_desc* d, const void* x, const void* w_pac
   const int nw = lat_dg_nw(mode);
   const dim3 grid((unsigned)ceil_div64(waves, nw)), block(64 * nw);
   const int lds = mode ? ks * a.kl * 2048 : 0;
-#define SFVOS_LAT3(KSv, TINv, ACCv, MODEv)                                                         \
-  if (ks == KSv && d->t_in == TINv && (d->accumulate != 0) == ACCv && mode == MODEv) {             \
-    auto kern = lateral_dgrad_kernel<KSv, TINv, ACCv, MODEv>;                                      \
-    static LdsAttrOnce once;                                                                       \
-    if (int rc = once.ensure((const void*)kern, LAT_DG_BIG_LDS, "lateral_dgrad")) return rc;       \
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, a);                                         \
-    return check_launch("lateral_dgrad");                                                          \
-  }
+#define SFVOS_LAT3(KSv, TINv, ACCv, MODEv)                                                                          \
+  if (ks == KSv && d->t_in == TINv && (d->accumulate != 0) == ACCv && mode == MODEv)                              \
+    return launch_lds<lateral_dgrad_kernel<KSv, TINv, ACCv, MODEv>>(grid, block, lds, LAT_DG_BIG_LDS, stream,       \
+                                                                    "lateral_dgrad", a);
 #define SFVOS_LAT2(KSv, TINv, ACCv) \
   SFVOS_LAT3(KSv, TINv, ACCv, 0) SFVOS_LAT3(KSv, TINv, ACCv, 1) SFVOS_LAT3(KSv, TINv, ACCv, 2) SFVOS_LAT3(KSv, TINv, ACCv, 3)
 #define SFVOS_LAT(KSv, TINv) SFVOS_LAT2(KSv, TINv, true) SFVOS_LAT2(KSv, TINv, false)

@@ -57,21 +57,6 @@ constexpr int LWG_NW = 8;        // waves per workgroup
 constexpr int LWG_MAX_NTW = 8;   // taps per wave (x one channel half): 128 accumulator registers; 4 tap blocks -> 32 taps per group
 constexpr int LWG_MAX_RING = 6;
 
-// s_waitcnt vmcnt(n) for a wave-uniform runtime n (the instruction takes an immediate)
-__device__ __forceinline__ void wait_vmcnt(int n) {
-#define SFVOS_VMW(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-  switch (n) {
-    SFVOS_VMW(0) SFVOS_VMW(1) SFVOS_VMW(2) SFVOS_VMW(3) SFVOS_VMW(4) SFVOS_VMW(5) SFVOS_VMW(6) SFVOS_VMW(7)
-    SFVOS_VMW(8) SFVOS_VMW(9) SFVOS_VMW(10) SFVOS_VMW(11) SFVOS_VMW(12) SFVOS_VMW(13) SFVOS_VMW(14) SFVOS_VMW(15)
-    SFVOS_VMW(16) SFVOS_VMW(17) SFVOS_VMW(18) SFVOS_VMW(19) SFVOS_VMW(20) SFVOS_VMW(21) SFVOS_VMW(22) SFVOS_VMW(23)
-    SFVOS_VMW(24) SFVOS_VMW(25) SFVOS_VMW(26) SFVOS_VMW(27) SFVOS_VMW(28) SFVOS_VMW(29) SFVOS_VMW(30) SFVOS_VMW(31)
-    SFVOS_VMW(32) SFVOS_VMW(33) SFVOS_VMW(34) SFVOS_VMW(35) SFVOS_VMW(36) SFVOS_VMW(37) SFVOS_VMW(38) SFVOS_VMW(39)
-    SFVOS_VMW(40) SFVOS_VMW(41) SFVOS_VMW(42) SFVOS_VMW(43) SFVOS_VMW(44) SFVOS_VMW(45) SFVOS_VMW(46) SFVOS_VMW(47)
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;   // more than the counter holds: drain
-  }
-#undef SFVOS_VMW
-}
-
 // SUB: 16-position sub-tiles per stage (a stage copies SUB KB contiguous bytes per x frame: longer DRAM bursts)
 template <int NTW, int TOUT, int SUB>
 __global__ __launch_bounds__(64 * LWG_NW) void lateral_wgrad_kernel(LatWgArgs a) {
@@ -165,7 +150,7 @@ __global__ __launch_bounds__(64 * LWG_NW) void lateral_wgrad_kernel(LatWgArgs a)
   for (int s = 0; s < R - 1 && s < S; ++s) issue(s);
   for (int s = 0; s < S; ++s) {
     // stage s has landed once at most the pieces of the min(R - 2, S - 1 - s) younger stages are outstanding
-    wait_vmcnt(npw * min(R - 2, S - 1 - s));
+    wait_vmcnt<47>(npw * min(R - 2, S - 1 - s));
     __syncthreads();   // everybody's pieces of stage s are in LDS; everybody is done reading stage s - 1
     if (s + R - 1 < S) issue(s + R - 1);   // into the slot of stage s - 1
     if (live > 0 && !SFVOS_LWG_DBG(1)) {
@@ -206,21 +191,17 @@ struct LatWgPlan {
   int ntiles, per, nshare;
   long long grid;
   int lds;
+  LevelTable lv;          // 16 sub-position tiles
 };
 
-// Shapes this kernel covers, and how it is launched for them.
+// Shapes this kernel covers (of a descriptor make_wgrad_plan accepted), and how it is launched for them.
 static bool lateral_wgrad_plan(const sfvos_conv_desc* d, LatWgPlan* p) {
   const int t_out = d->t_in - d->kt + 1;
-  if (!(d->dtype == SFVOS_BF16 && d->taps == 1 && d->c_in == 32 && d->c_out == 64 && d->pad_t == 0 && d->kt >= 1 &&
-        t_out >= 1 && t_out <= 3 && d->x_group_stride == 0 && d->x_frame_stride == 0 &&
-        d->y_frame_stride == 0 && d->t_offset >= 0 && d->t_offset + d->t_in <= d->t_alloc && d->ld_x % 8 == 0 &&
-        d->ld_x >= 32 && d->ld_y % 8 == 0 && d->ld_y >= 64 && d->batch >= 1 && d->pyr.n_levels >= 1 &&
-        d->pyr.n_levels <= SFVOS_MAX_LEVELS))
+  if (!(d->dtype == SFVOS_BF16 && d->taps == 1 && d->c_in == 32 && d->c_out == 64 && d->pad_t == 0 && t_out >= 1 &&
+        t_out <= 3 && d->x_group_stride == 0 && d->x_frame_stride == 0 && d->y_frame_stride == 0 && d->t_offset >= 0 &&
+        d->t_offset + d->t_in <= d->t_alloc && d->ld_x % 8 == 0 && d->ld_x >= 32 && d->ld_y % 8 == 0 && d->ld_y >= 64 &&
+        max_frame_positions(d) * d->ld_y * 2 < (1ll << 31)))
     return false;
-  for (int l = 0; l < d->pyr.n_levels; ++l) {
-    if (d->pyr.h[l] < 1 || d->pyr.w[l] < 1) return false;
-    if ((long long)d->pyr.h[l] * d->pyr.w[l] * (d->ld_x > d->ld_y ? d->ld_x : d->ld_y) * 2 >= (1ll << 31)) return false;
-  }
   const int cus = device_cu_count() > 0 ? device_cu_count() : 256;
   // Tap groups.  Measured inside the training step (conv_f2s1, kt = 20 / conv_f2s2, kt = 11; 1, 2, 4 groups): 52.7 / 48.6 /
   // 56.6 us and 32.6 / 34.4 / 42.2 us -- with many taps the halved slabs (kt x 8 KB per share, written and read again) pay
@@ -254,9 +235,8 @@ static bool lateral_wgrad_plan(const sfvos_conv_desc* d, LatWgPlan* p) {
   if (R < 2) return false;
   // counted waits: (R - 2) stages x at most ceil(pieces / 8) pieces per wave must fit the 6-bit counter
   while (R > 2 && (R - 2) * ceil_div(units * sub, LWG_NW) > 47) --R;
-  long long tiles = 0;
-  for (int l = 0; l < d->pyr.n_levels; ++l) tiles += (long long)d->batch * ceil_div(d->pyr.h[l] * d->pyr.w[l], 16 * sub);
-  if (tiles < 1 || tiles >= (1ll << 30)) return false;
+  const long long tiles = level_table(d, d->t_alloc, t_out, 0, 16 * sub, &p->lv);
+  if (tiles >= (1ll << 30)) return false;
   // shares: workgroups / groups, each with a contiguous run of the tiles; every share costs one slab of kt x 8 KB written
   // and read again, so tiny problems get fewer (at least 8 stages each)
   long long g = tiles / 8 > 0 ? tiles / 8 : 1;
@@ -295,37 +275,20 @@ int lateral_wgrad_try(const sfvos_conv_desc* d, const void* x, const void* dy, f
   if (const char* dbg = getenv("SFVOS_LWG_DEBUG")) a.debug = atoi(dbg);
 #endif
   a.ntiles = p.ntiles; a.per = p.per; a.nshare = p.nshare; a.groups = p.groups; a.dtg = p.dtg; a.ring = p.ring;
-  a.n = d->pyr.n_levels;
-  long long tiles = 0, px = 0;
-  for (int l = 0; l < SFVOS_MAX_LEVELS; ++l) {
-    const bool live = l < a.n;
-    const int HW = live ? d->pyr.h[l] * d->pyr.w[l] : 1;
-    a.HW[l] = HW;
-    a.tile_begin[l] = (int)tiles;
-    a.xpos[l] = (long long)d->batch * a.t_alloc * px;
-    a.ypos[l] = (long long)d->batch * a.t_out * px;
-    if (live) {
-      tiles += (long long)d->batch * ceil_div(HW, 16 * p.sub);
-      px += HW;
-    }
-  }
-  a.tile_begin[SFVOS_MAX_LEVELS] = (int)tiles;
+  copy_levels_1d(p.lv, &a.n, a.HW, a.tile_begin, a.xpos, a.ypos);
+  int rc = -1;
 #define SFVOS_LWG(NTWv, TOUTv) SFVOS_LWGS(NTWv, TOUTv, 1) SFVOS_LWGS(NTWv, TOUTv, 2)
-#define SFVOS_LWGS(NTWv, TOUTv, SUBv)                                                                \
-  if (p.ntw == NTWv && a.t_out == TOUTv && p.sub == SUBv) {                                          \
-    auto kern = lateral_wgrad_kernel<NTWv, TOUTv, SUBv>;                                             \
-    static LdsAttrOnce once;                                                                         \
-    if (int rc = once.ensure((const void*)kern, 160 * 1024, "lateral_wgrad")) return rc;             \
-    hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(64 * LWG_NW), p.lds, stream, a);           \
-    if (int rc = check_launch("lateral_wgrad")) return rc;                                           \
-    return launch_wgrad_reduce((const float*)workspace, p.nshare, 64, 32, d->kt, 1, grad_w, accumulate, stream); \
-  }
+#define SFVOS_LWGS(NTWv, TOUTv, SUBv)                                                                                    \
+  if (p.ntw == NTWv && a.t_out == TOUTv && p.sub == SUBv)                                                                \
+    rc = launch_lds<lateral_wgrad_kernel<NTWv, TOUTv, SUBv>>(dim3((unsigned)p.grid), dim3(64 * LWG_NW), p.lds, 160 * 1024, \
+                                                             stream, "lateral_wgrad", a);
 #define SFVOS_LWG3(NTWv) SFVOS_LWG(NTWv, 1) SFVOS_LWG(NTWv, 2) SFVOS_LWG(NTWv, 3)
   SFVOS_LWG3(1) SFVOS_LWG3(2) SFVOS_LWG3(3) SFVOS_LWG3(4) SFVOS_LWG3(5) SFVOS_LWG3(6) SFVOS_LWG3(7) SFVOS_LWG3(8)
 #undef SFVOS_LWG3
 #undef SFVOS_LWG
 #undef SFVOS_LWGS
-  return -1;
+  if (rc != SFVOS_OK) return rc;
+  return launch_wgrad_reduce((const float*)workspace, p.nshare, 64, 32, d->kt, 1, grad_w, accumulate, stream);
 }
 
 }  // namespace sfvos

@@ -27,14 +27,6 @@
 
 namespace sfvos {
 
-struct WgradLevels {
-  int n;
-  int H[SFVOS_MAX_LEVELS], W[SFVOS_MAX_LEVELS], tiles_h[SFVOS_MAX_LEVELS], tiles_w[SFVOS_MAX_LEVELS];
-  int tile_begin[SFVOS_MAX_LEVELS + 1];  // first pixel tile of each level (tiles enumerate level, clip, th, tw)
-  long long xpos[SFVOS_MAX_LEVELS];      // first position of the level in the x / dy pyramid buffers
-  long long ypos[SFVOS_MAX_LEVELS];
-};
-
 struct WgradArgs {
   const char* x;
   const char* dy;
@@ -43,7 +35,7 @@ struct WgradArgs {
   long long x_group_bytes;  // 0: x is pyramid NDHWC (pitch ld_x); else bytes between its 64-byte channel groups (bf16)
   int n_blocks, c_blocks, dt_blocks, psplit;
   int ntiles;  // over all levels and clips
-  WgradLevels lv;
+  LevelTable lv;  // TH x 16 pixel tiles
 };
 
 // NXS: x tiles a stage may copy ahead (2: one frame per stage is new when t_out > 1; DG: a conv with ONE output frame
@@ -609,17 +601,12 @@ struct WgradPlan {
             // 4: (1,1,8) 3x3 c_in 32 with ONE output frame (bf16): 4-row tiles, ring of two stages
   int NTN, NTC, DG, TH, FPR;   // FPR: 16x16x32 MFMAs, 1 = frame-paired stages (bf16 3x3, c_in >= 64, even t_out >= 4), 2 = row pairs
   int n_blocks, c_blocks, dt_blocks, psplit, t_out, ntiles;
-  WgradLevels lv;
+  LevelTable lv;
 };
 
 static int make_wgrad_plan(const sfvos_conv_desc* d, WgradPlan* p) {
-  SFVOS_REQUIRE(d != nullptr, "wgrad: null desc");
-  SFVOS_REQUIRE(d->struct_size == (int)sizeof(sfvos_conv_desc),
-                "wgrad: sfvos_conv_desc.struct_size is %d, this library's struct has %d bytes (stale binding?)",
-                d->struct_size, (int)sizeof(sfvos_conv_desc));
-  SFVOS_REQUIRE(d->dtype == SFVOS_F32 || d->dtype == SFVOS_BF16, "wgrad: bad dtype");
-  SFVOS_REQUIRE(d->taps == 9 || d->taps == 1, "wgrad: taps must be 9 or 1");
-  SFVOS_REQUIRE(d->c_in % 32 == 0 && d->c_out % 32 == 0 && d->c_in > 0 && d->c_out > 0, "wgrad: channels % 32");
+  if (int rc = check_conv_desc(d, "wgrad")) return rc;
+  SFVOS_REQUIRE(d->dtype != SFVOS_FP8, "wgrad: e4m3 operands have no weight gradient here");
   SFVOS_REQUIRE(d->pad_t == 0, "wgrad: only forward convs (pad_t == 0) have a weight gradient here");
   SFVOS_REQUIRE(d->x_frame_stride == 0 && d->y_frame_stride == 0,
                 "wgrad: frame-major ring buffers are an inference-only layout");
@@ -668,28 +655,10 @@ static int make_wgrad_plan(const sfvos_conv_desc* d, WgradPlan* p) {
     // two-tile look-ahead of the other configurations each stage waited a memory round trip for the other six.
     p->cfg = 4; p->TH = 4; p->DG = 8; p->FPR = 0;
   }
-  SFVOS_REQUIRE(d->pyr.n_levels >= 1 && d->pyr.n_levels <= SFVOS_MAX_LEVELS, "wgrad: n_levels out of range");
-  SFVOS_REQUIRE(d->batch >= 1 && d->t_alloc >= 1 && d->t_offset > -(1 << 20) && d->t_offset < (1 << 20) &&
-                d->t_in < (1 << 20), "wgrad: bad x window");  // frames of the window outside [0, t_alloc) are zeros
-  WgradLevels& lv = p->lv;
-  lv.n = d->pyr.n_levels;
-  long long tiles = 0, px = 0;
-  for (int l = 0; l < SFVOS_MAX_LEVELS; ++l) {
-    const bool live = l < lv.n;
-    const int H = live ? d->pyr.h[l] : 1, W = live ? d->pyr.w[l] : 1;
-    SFVOS_REQUIRE(H >= 1 && W >= 1, "wgrad: level %d has bad extent", l);
-    lv.H[l] = H; lv.W[l] = W;
-    lv.tiles_h[l] = ceil_div(H, p->TH); lv.tiles_w[l] = ceil_div(W, 16);
-    lv.tile_begin[l] = (int)tiles;
-    lv.xpos[l] = (long long)d->batch * d->t_alloc * px;
-    lv.ypos[l] = (long long)d->batch * p->t_out * px;
-    if (live) {
-      tiles += (long long)d->batch * lv.tiles_h[l] * lv.tiles_w[l];
-      px += (long long)H * W;
-    }
-    SFVOS_REQUIRE(tiles < (1ll << 30), "wgrad: too many tiles");
-  }
-  lv.tile_begin[SFVOS_MAX_LEVELS] = (int)tiles;
+  const long long tiles = level_table(d, d->t_alloc, p->t_out, p->TH, 16, &p->lv);
+  SFVOS_REQUIRE(tiles < (1ll << 30), "wgrad: too many tiles");
+  long long px = 0;  // positions of one frame over all levels
+  for (int l = 0; l < p->lv.n; ++l) px += (long long)p->lv.H[l] * p->lv.W[l];
   p->n_blocks = ceil_div(d->c_out, 32 * p->NTN);
   p->c_blocks = ceil_div(d->c_in, 32 * p->NTC);
   p->dt_blocks = ceil_div(d->kt, p->DG);
@@ -726,12 +695,9 @@ static int make_wgrad_plan(const sfvos_conv_desc* d, WgradPlan* p) {
 
 template <int DT, int TAPS, int NTN, int NTC, int DG, int TH, int R, int NXS = 2, int KS = 1, int FPR = 0>
 static int launch_wgrad(const WgradArgs& a, long long grid, hipStream_t stream) {
-  typedef WgradCfg<DT, TAPS, NTN, NTC, DG, TH, R, NXS, KS, FPR> C;
-  auto kern = wgrad_kernel<DT, TAPS, NTN, NTC, DG, TH, R, NXS, KS, FPR>;
-  static LdsAttrOnce once;
-  if (int rc = once.ensure((const void*)kern, C::LDS_BYTES, "wgrad")) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), C::LDS_BYTES, stream, a);
-  return check_launch("wgrad");
+  constexpr int LDS = WgradCfg<DT, TAPS, NTN, NTC, DG, TH, R, NXS, KS, FPR>::LDS_BYTES;
+  return launch_lds<wgrad_kernel<DT, TAPS, NTN, NTC, DG, TH, R, NXS, KS, FPR>>(dim3((unsigned)grid), dim3(512), LDS, LDS,
+                                                                                stream, "wgrad", a);
 }
 
 }  // namespace sfvos
@@ -741,18 +707,12 @@ using namespace sfvos;
 // The lateral k x 1 x 1 convs (32 -> 64 channels, bf16) have a kernel of their own (lateral_wgrad.hip: all kt taps per
 // workgroup, x and dy read once), and so has the kt x 3 x 3 conv 32 -> 32 with one output frame (wgrad_t1.hip).  The workspace is sized for whichever of the two kernels needs more, so the generic one
 // stays available as the fallback.
-static bool lateral_wgrad_wanted(const sfvos_conv_desc* d) {
-#ifdef SFVOS_DIAG
-  if (getenv("SFVOS_NO_LATERAL_KERNEL")) return false;
-#endif
-  return d != nullptr && d->struct_size == (int)sizeof(sfvos_conv_desc);
-}
 
 extern "C" size_t sfvos_conv3d_wgrad_workspace_bytes(const sfvos_conv_desc* d) {
   WgradPlan p;
   if (make_wgrad_plan(d, &p) != SFVOS_OK) return 0;
   size_t n = (size_t)p.psplit * d->c_out * d->c_in * d->kt * d->taps * sizeof(float);
-  if (lateral_wgrad_wanted(d)) {
+  if (lateral_kernels_on()) {
     size_t m = lateral_wgrad_workspace_bytes(d);
     if (m > n) n = m;
     m = wgrad_t1_workspace_bytes(d);
@@ -767,7 +727,7 @@ extern "C" int sfvos_conv3d_wgrad(const sfvos_conv_desc* d, const void* x, const
   int rc = make_wgrad_plan(d, &p);
   if (rc != SFVOS_OK) return rc;
   SFVOS_REQUIRE(x && dy && grad_w && workspace, "wgrad: null pointer");
-  if (lateral_wgrad_wanted(d)) {
+  if (lateral_kernels_on()) {
     rc = lateral_wgrad_try(d, x, dy, grad_w, accumulate, workspace, (hipStream_t)stream);
     if (rc >= 0) return rc;
     bool t1_ok = true;

@@ -54,22 +54,8 @@ struct T1Args {
   int t_alloc, t_offset, kt, ld_x, ld_y, batch;
   int ntiles, per, nshare;   // 16 x 16 tiles over all levels and clips; tiles per pixel share; shares (= slabs)
   int debug;                 // diagnostic builds only: 1 no fragment reads / MFMAs, 2 no x copies, 4 no dy copies, 8 no sums / slabs
-  int n;                     // levels
-  int H[SFVOS_MAX_LEVELS], W[SFVOS_MAX_LEVELS], tiles_h[SFVOS_MAX_LEVELS], tiles_w[SFVOS_MAX_LEVELS];
-  int tile_begin[SFVOS_MAX_LEVELS + 1];
-  long long xpos[SFVOS_MAX_LEVELS], ypos[SFVOS_MAX_LEVELS];
+  LevelTable lv;              // 16 x 16 tiles
 };
-
-// s_waitcnt vmcnt(n) for a wave-uniform runtime n in [0, 10] (two younger stages of at most five pieces)
-__device__ __forceinline__ void t1_wait_vmcnt(int n) {
-#define SFVOS_VMW(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-  switch (n) {
-    SFVOS_VMW(1) SFVOS_VMW(2) SFVOS_VMW(3) SFVOS_VMW(4) SFVOS_VMW(5) SFVOS_VMW(6) SFVOS_VMW(7) SFVOS_VMW(8) SFVOS_VMW(9)
-    SFVOS_VMW(10)
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-#undef SFVOS_VMW
-}
 
 __global__ __launch_bounds__(64 * T1_NW) void wgrad_t1_kernel(T1Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -114,13 +100,13 @@ __global__ __launch_bounds__(64 * T1_NW) void wgrad_t1_kernel(T1Args a) {
     lvl = l;
 #pragma unroll
     for (int k = 0; k < SFVOS_MAX_LEVELS; ++k)
-      if (k == l) { H = a.H[k]; W = a.W[k]; tiles_h = a.tiles_h[k]; tiles_w = a.tiles_w[k]; xpos = a.xpos[k]; ypos = a.ypos[k]; }
+      if (k == l) { H = a.lv.H[k]; W = a.lv.W[k]; tiles_h = a.lv.tiles_h[k]; tiles_w = a.lv.tiles_w[k]; xpos = a.lv.xpos[k]; ypos = a.lv.ypos[k]; }
   };
   {
     int l0 = 0, begin = 0;
 #pragma unroll
     for (int l = 1; l < SFVOS_MAX_LEVELS; ++l)
-      if (l < a.n && tile_begin >= a.tile_begin[l]) { l0 = l; begin = a.tile_begin[l]; }
+      if (l < a.lv.n && tile_begin >= a.lv.tile_begin[l]) { l0 = l; begin = a.lv.tile_begin[l]; }
     set_level(l0);
     int k = tile_begin - begin;
     tw = k % tiles_w; k /= tiles_w;
@@ -150,7 +136,7 @@ __global__ __launch_bounds__(64 * T1_NW) void wgrad_t1_kernel(T1Args a) {
       tw = 0;
       if (++th == tiles_h) {
         th = 0;
-        if (++cb == a.batch) { cb = 0; set_level(lvl + 1 < a.n ? lvl + 1 : lvl); }
+        if (++cb == a.batch) { cb = 0; set_level(lvl + 1 < a.lv.n ? lvl + 1 : lvl); }
       }
     }
   };
@@ -175,7 +161,7 @@ __global__ __launch_bounds__(64 * T1_NW) void wgrad_t1_kernel(T1Args a) {
   for (int s = 0; s < T1_R - 1 && s < S; ++s) issue(s);
   for (int s = 0; s < S; ++s) {
     // stage s has landed once at most the pieces of the min(R - 2, S - 1 - s) younger stages are outstanding
-    t1_wait_vmcnt(npw * min(T1_R - 2, S - 1 - s));
+    wait_vmcnt<10, 1>(npw * min(T1_R - 2, S - 1 - s));
     __syncthreads();   // everybody's pieces of stage s are in LDS; everybody is done reading stage s - 1
     if (s + T1_R - 1 < S) issue(s + T1_R - 1);   // into the slot of stage s - 1
     if (SFVOS_T1_DBG(1)) continue;
@@ -232,21 +218,18 @@ __global__ __launch_bounds__(64 * T1_NW) void wgrad_t1_kernel(T1Args a) {
 struct T1Plan {
   int ntiles, per, nshare;
   long long grid;
+  LevelTable lv;
 };
 
+// Shapes this kernel covers (of a descriptor make_wgrad_plan accepted), and how it is launched for them.
 static bool wgrad_t1_plan(const sfvos_conv_desc* d, T1Plan* p) {
   if (!(d->dtype == SFVOS_BF16 && d->taps == 9 && d->c_in == 32 && d->c_out == 32 && d->pad_t == 0 && d->kt >= 2 &&
         d->t_in == d->kt && d->x_group_stride == 0 && d->x_frame_stride == 0 && d->y_frame_stride == 0 &&
         d->t_offset >= 0 && d->t_offset + d->t_in <= d->t_alloc && d->ld_x % 8 == 0 && d->ld_x >= 32 && d->ld_y % 8 == 0 &&
-        d->ld_y >= 32 && d->batch >= 1 && d->pyr.n_levels >= 1 && d->pyr.n_levels <= SFVOS_MAX_LEVELS))
+        d->ld_y >= 32 && max_frame_positions(d) * d->ld_y * 2 < (1ll << 31)))
     return false;
-  long long tiles = 0;
-  for (int l = 0; l < d->pyr.n_levels; ++l) {
-    if (d->pyr.h[l] < 1 || d->pyr.w[l] < 1) return false;
-    if ((long long)d->pyr.h[l] * d->pyr.w[l] * (d->ld_x > d->ld_y ? d->ld_x : d->ld_y) * 2 >= (1ll << 31)) return false;
-    tiles += (long long)d->batch * ceil_div(d->pyr.h[l], T1_TH) * ceil_div(d->pyr.w[l], T1_TW);
-  }
-  if (tiles < 1 || tiles >= (1ll << 30)) return false;
+  const long long tiles = level_table(d, d->t_alloc, 1, T1_TH, T1_TW, &p->lv);
+  if (tiles >= (1ll << 30)) return false;
   const int cus = device_cu_count() > 0 ? device_cu_count() : 256;
   // shares: one round of workgroups (cus / kt shares x kt taps); every share costs one slab written and read again, so tiny
   // problems get fewer (at least 4 stages each)
@@ -281,26 +264,9 @@ int wgrad_t1_try(const sfvos_conv_desc* d, const void* x, const void* dy, float*
 #ifdef SFVOS_DIAG
   if (const char* dbg = getenv("SFVOS_T1_DEBUG")) a.debug = atoi(dbg);
 #endif
-  a.n = d->pyr.n_levels;
-  long long tiles = 0, px = 0;
-  for (int l = 0; l < SFVOS_MAX_LEVELS; ++l) {
-    const bool live = l < a.n;
-    const int H = live ? d->pyr.h[l] : 1, W = live ? d->pyr.w[l] : 1;
-    a.H[l] = H; a.W[l] = W;
-    a.tiles_h[l] = ceil_div(H, T1_TH); a.tiles_w[l] = ceil_div(W, T1_TW);
-    a.tile_begin[l] = (int)tiles;
-    a.xpos[l] = (long long)d->batch * d->t_alloc * px;
-    a.ypos[l] = (long long)d->batch * px;   // t_out = 1
-    if (live) {
-      tiles += (long long)d->batch * a.tiles_h[l] * a.tiles_w[l];
-      px += (long long)H * W;
-    }
-  }
-  a.tile_begin[SFVOS_MAX_LEVELS] = (int)tiles;
-  static LdsAttrOnce once;
-  if (int rc = once.ensure((const void*)wgrad_t1_kernel, T1_LDS, "wgrad_t1")) return rc;
-  hipLaunchKernelGGL(wgrad_t1_kernel, dim3((unsigned)p.grid), dim3(64 * T1_NW), T1_LDS, stream, a);
-  if (int rc = check_launch("wgrad_t1")) return rc;
+  a.lv = p.lv;
+  if (int rc = launch_lds<wgrad_t1_kernel>(dim3((unsigned)p.grid), dim3(64 * T1_NW), T1_LDS, T1_LDS, stream, "wgrad_t1", a))
+    return rc;
   return launch_wgrad_reduce((const float*)workspace, p.nshare, 32, 32, d->kt, 9, grad_w, accumulate, stream);
 }
 
