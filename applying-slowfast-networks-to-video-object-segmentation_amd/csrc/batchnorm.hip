@@ -328,14 +328,6 @@ __global__ __launch_bounds__(32 * RL) void bn_bwd_finalize_kernel(const float* p
   }
 }
 
-static int check_act(const char* what, int dtype, int C, int ld_a, int ld_b) {
-  const int ce = dtype == SFVOS_BF16 ? 8 : 4;
-  SFVOS_REQUIRE(dtype == SFVOS_F32 || dtype == SFVOS_BF16, "%s: bad dtype", what);
-  SFVOS_REQUIRE(C > 0 && C % 32 == 0 && C <= 256, "%s: C must be a multiple of 32, <= 256", what);
-  SFVOS_REQUIRE(ld_a >= C && ld_b >= C && ld_a % ce == 0 && ld_b % ce == 0, "%s: bad pitch", what);
-  return SFVOS_OK;
-}
-
 }  // namespace sfvos
 
 using namespace sfvos;
@@ -397,15 +389,11 @@ extern "C" int sfvos_bn_apply(const void* x, int ld_x, void* y, int ld_y, int dt
   rc = make_run_upd(running, &ru, "bn_apply");
   if (rc) return rc;
   SFVOS_REQUIRE(x && y && scale && shift && coef_stride >= C, "bn_apply: bad pointer / coef_stride");
-  const int ce = dtype == SFVOS_BF16 ? 8 : 4;
-  const unsigned grid = grid_for(lt.mb[SFVOS_MAX_LEVELS] * (C / ce), 256 * 4);
-  hipStream_t s = (hipStream_t)stream;
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(bn_apply_kernel<SFVOS_F32>, dim3(grid), dim3(256), 0, s, (const char*)x, ld_x,
-                                 (char*)y, ld_y, lt, C, scale, shift, coef_stride, relu, ru),
-              hipLaunchKernelGGL(bn_apply_kernel<SFVOS_BF16>, dim3(grid), dim3(256), 0, s, (const char*)x, ld_x,
-                                 (char*)y, ld_y, lt, C, scale, shift, coef_stride, relu, ru));
-  return check_launch("bn_apply");
+  const unsigned grid = grid_for(lt.mb[SFVOS_MAX_LEVELS] * (C / (16 / elt_bytes(dtype))), 256 * 4);
+  return launch_dt(dtype, "bn_apply", [&](auto dt) {
+    hipLaunchKernelGGL(bn_apply_kernel<dt>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const char*)x, ld_x,
+                       (char*)y, ld_y, lt, C, scale, shift, coef_stride, relu, ru);
+  });
 }
 
 extern "C" int sfvos_bn_apply_fp8(const void* x, int ld_x, void* y, int ld_y, const sfvos_levels* lv, int C,
@@ -444,19 +432,12 @@ extern "C" int sfvos_bn_bwd_reduce(const void* dy, int ld_dy, const void* x, int
   if (rc) return rc;
   SFVOS_REQUIRE(dy && x && scale && shift && mean && rstd && part && coef_stride >= C, "bn_bwd_reduce: bad argument");
   const unsigned grid = (unsigned)lt.blk_begin[SFVOS_MAX_LEVELS];
-  hipStream_t s = (hipStream_t)stream;
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL((bn_bwd_kernel<SFVOS_F32, false>), dim3(grid), dim3(BNB_THREADS), 0, s,
-                                 (const char*)dy, ld_dy, (const char*)x, ld_x, (char*)nullptr, 0, lt, C, scale, shift,
-                                 mean, rstd, coef_stride, relu, (const float*)nullptr, (const float*)nullptr,
-                                 (const float*)nullptr, part, (const float*)nullptr, (const float*)nullptr,
-                                 (float*)nullptr, (float*)nullptr, 0),
-              hipLaunchKernelGGL((bn_bwd_kernel<SFVOS_BF16, false>), dim3(grid), dim3(BNB_THREADS), 0, s,
-                                 (const char*)dy, ld_dy, (const char*)x, ld_x, (char*)nullptr, 0, lt, C, scale, shift,
-                                 mean, rstd, coef_stride, relu, (const float*)nullptr, (const float*)nullptr,
-                                 (const float*)nullptr, part, (const float*)nullptr, (const float*)nullptr,
-                                 (float*)nullptr, (float*)nullptr, 0));
-  return check_launch("bn_bwd_reduce");
+  return launch_dt(dtype, "bn_bwd_reduce", [&](auto dt) {
+    hipLaunchKernelGGL((bn_bwd_kernel<dt, false>), dim3(grid), dim3(BNB_THREADS), 0, (hipStream_t)stream,
+                       (const char*)dy, ld_dy, (const char*)x, ld_x, (char*)nullptr, 0, lt, C, scale, shift, mean, rstd,
+                       coef_stride, relu, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, part,
+                       (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (float*)nullptr, 0);
+  });
 }
 
 extern "C" int sfvos_bn_bwd_finalize(const float* part, const sfvos_levels* lv, const float* gamma, const float* mean,
@@ -485,18 +466,13 @@ extern "C" int sfvos_bn_bwd_apply(const void* dy, int ld_dy, const void* x, int 
   if (rc) return rc;
   SFVOS_REQUIRE(dy && x && dx && scale && shift && coefA && coefB && coefK && coef_stride >= C,
                 "bn_bwd_apply: bad argument");
-  SFVOS_REQUIRE(ld_dx >= C && ld_dx % (dtype == SFVOS_BF16 ? 8 : 4) == 0, "bn_bwd_apply: bad ld_dx");
+  SFVOS_REQUIRE(ld_dx >= C && ld_dx % (16 / elt_bytes(dtype)) == 0, "bn_bwd_apply: bad ld_dx");
   SFVOS_REQUIRE(!(dgamma || dbeta) || (sum_dz && sum_dzx), "bn_bwd_apply: dgamma / dbeta need the per-level sums");
   const unsigned grid = (unsigned)lt.blk_begin[SFVOS_MAX_LEVELS];
-  hipStream_t s = (hipStream_t)stream;
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL((bn_bwd_kernel<SFVOS_F32, true>), dim3(grid), dim3(BNB_THREADS), 0, s,
-                                 (const char*)dy, ld_dy, (const char*)x, ld_x, (char*)dx, ld_dx, lt, C, scale, shift,
-                                 (const float*)nullptr, (const float*)nullptr, coef_stride, relu, coefA, coefB, coefK,
-                                 bias_part, sum_dz, sum_dzx, dgamma, dbeta, accumulate),
-              hipLaunchKernelGGL((bn_bwd_kernel<SFVOS_BF16, true>), dim3(grid), dim3(BNB_THREADS), 0, s,
-                                 (const char*)dy, ld_dy, (const char*)x, ld_x, (char*)dx, ld_dx, lt, C, scale, shift,
-                                 (const float*)nullptr, (const float*)nullptr, coef_stride, relu, coefA, coefB, coefK,
-                                 bias_part, sum_dz, sum_dzx, dgamma, dbeta, accumulate));
-  return check_launch("bn_bwd_apply");
+  return launch_dt(dtype, "bn_bwd_apply", [&](auto dt) {
+    hipLaunchKernelGGL((bn_bwd_kernel<dt, true>), dim3(grid), dim3(BNB_THREADS), 0, (hipStream_t)stream,
+                       (const char*)dy, ld_dy, (const char*)x, ld_x, (char*)dx, ld_dx, lt, C, scale, shift,
+                       (const float*)nullptr, (const float*)nullptr, coef_stride, relu, coefA, coefB, coefK, bias_part,
+                       sum_dz, sum_dzx, dgamma, dbeta, accumulate);
+  });
 }

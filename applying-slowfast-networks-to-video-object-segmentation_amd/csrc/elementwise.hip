@@ -241,6 +241,15 @@ static bool planes_vectorizable(const float* src, const PlanarView& v) {
          v.C % 8 == 0;
 }
 
+// The frames of a single-level layout pass (T x C x H x W floats at element strides st, sc, sh, sw) and the buffer on
+// the other side of the pass.
+static int planar_frames(const void* a, const void* b, int64_t st, int64_t sc, int64_t sh, int64_t sw, int T, int C,
+                         int H, int W, PlanarView* v, const char* what) {
+  SFVOS_REQUIRE(a && b && T > 0 && C > 0 && H > 0 && W > 0, "%s: bad argument", what);
+  *v = PlanarView{st, sc, sh, sw, T, C, H, W};
+  return SFVOS_OK;
+}
+
 template <int DT>
 __device__ __forceinline__ void from_ndhwc_body(const char* __restrict__ src, int ld, float* dst, const PlanarView& v,
                                                 int accumulate, int bx, int by, int bz) {
@@ -462,9 +471,9 @@ using namespace sfvos;
 
 extern "C" int sfvos_frames_to_ndhwc(const float* src, int64_t st, int64_t sc, int64_t sh, int64_t sw, void* dst,
                                      int dtype, int T, int C, int H, int W, int ld, sfvos_stream_t stream) {
-  SFVOS_REQUIRE(src && dst && T > 0 && C > 0 && H > 0 && W > 0 && ld >= C, "frames_to_ndhwc: bad argument");
-  SFVOS_REQUIRE(C % 8 == 0 && ld % 8 == 0, "frames_to_ndhwc: C and ld must be multiples of 8");
-  PlanarView v{st, sc, sh, sw, T, C, H, W};
+  PlanarView v;
+  if (int rc = planar_frames(src, dst, st, sc, sh, sw, T, C, H, W, &v, "frames_to_ndhwc")) return rc;
+  SFVOS_REQUIRE(ld >= C && C % 8 == 0 && ld % 8 == 0, "frames_to_ndhwc: C and ld must be multiples of 8, ld >= C");
   dim3 grid((unsigned)ceil_div64((int64_t)H * W, 64), (unsigned)ceil_div(C, 64), (unsigned)T);
   hipStream_t s = (hipStream_t)stream;
   if (dtype == SFVOS_BF16 && planes_vectorizable(src, v) && ((size_t)dst & 15) == 0) {
@@ -472,20 +481,19 @@ extern "C" int sfvos_frames_to_ndhwc(const float* src, int64_t st, int64_t sc, i
     hipLaunchKernelGGL(to_ndhwc_bf16_vec_kernel, gridv, dim3(256), 0, s, src, v, (char*)dst, ld, 1 << 30, 0ll);
     return check_launch("frames_to_ndhwc");
   }
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(to_ndhwc_kernel<SFVOS_F32>, grid, dim3(256), 0, s, src, v, (char*)dst, ld, 1 << 30, 0ll),
-              hipLaunchKernelGGL(to_ndhwc_kernel<SFVOS_BF16>, grid, dim3(256), 0, s, src, v, (char*)dst, ld, 1 << 30, 0ll));
-  return check_launch("frames_to_ndhwc");
+  return launch_dt(dtype, "frames_to_ndhwc", [&](auto dt) {
+    hipLaunchKernelGGL(to_ndhwc_kernel<dt>, grid, dim3(256), 0, s, src, v, (char*)dst, ld, 1 << 30, 0ll);
+  });
 }
 
 extern "C" int sfvos_frames_to_groups(const float* src, int64_t st, int64_t sc, int64_t sh, int64_t sw, void* dst,
                                       int dtype, int T, int C, int H, int W, int64_t group_stride,
                                       sfvos_stream_t stream) {
-  SFVOS_REQUIRE(src && dst && T > 0 && C > 0 && H > 0 && W > 0, "frames_to_groups: bad argument");
+  PlanarView v;
+  if (int rc = planar_frames(src, dst, st, sc, sh, sw, T, C, H, W, &v, "frames_to_groups")) return rc;
   SFVOS_REQUIRE(dtype == SFVOS_BF16, "frames_to_groups: the channel-group-major layout is bf16 only");
   SFVOS_REQUIRE(C % 32 == 0 && group_stride >= (int64_t)T * H * W * 32 && group_stride % 8 == 0,
                 "frames_to_groups: C must be a multiple of 32 and group_stride >= T*H*W*32");
-  PlanarView v{st, sc, sh, sw, T, C, H, W};
   if (planes_vectorizable(src, v) && ((size_t)dst & 15) == 0) {
     dim3 gridv((unsigned)ceil_div64((int64_t)H * W, 128), (unsigned)ceil_div(C, 64), (unsigned)T);
     hipLaunchKernelGGL(to_ndhwc_bf16_vec_kernel, gridv, dim3(256), 0, (hipStream_t)stream, src, v, (char*)dst, 32, 32,
@@ -501,10 +509,11 @@ extern "C" int sfvos_frames_to_groups(const float* src, int64_t st, int64_t sc, 
 extern "C" int sfvos_frames_to_groups_fp8(const float* src, int64_t st, int64_t sc, int64_t sh, int64_t sw, void* dst,
                                           int T, int C, int H, int W, int64_t group_stride, float scale,
                                           int* sat_count, sfvos_stream_t stream) {
-  SFVOS_REQUIRE(src && dst && T > 0 && C > 0 && H > 0 && W > 0 && scale > 0.f, "frames_to_groups_fp8: bad argument");
+  PlanarView v;
+  if (int rc = planar_frames(src, dst, st, sc, sh, sw, T, C, H, W, &v, "frames_to_groups_fp8")) return rc;
+  SFVOS_REQUIRE(scale > 0.f, "frames_to_groups_fp8: scale must be positive");
   SFVOS_REQUIRE(C % 64 == 0 && group_stride >= (int64_t)T * H * W * 64 && group_stride % 16 == 0,
                 "frames_to_groups_fp8: C must be a multiple of 64 and group_stride >= T*H*W*64");
-  PlanarView v{st, sc, sh, sw, T, C, H, W};
   dim3 grid((unsigned)ceil_div64((int64_t)H * W, 64), (unsigned)ceil_div(C, 64), (unsigned)T);
   hipLaunchKernelGGL(to_ndhwc_kernel<SFVOS_FP8>, grid, dim3(256), 0, (hipStream_t)stream, src, v, (char*)dst, 64, 64,
                      (long long)group_stride, scale, sat_count);
@@ -513,8 +522,8 @@ extern "C" int sfvos_frames_to_groups_fp8(const float* src, int64_t st, int64_t 
 
 extern "C" int sfvos_frames_absmax(const float* src, int64_t st, int64_t sc, int64_t sh, int64_t sw, int T, int C,
                                    int H, int W, float* amax, sfvos_stream_t stream) {
-  SFVOS_REQUIRE(src && amax && T > 0 && C > 0 && H > 0 && W > 0, "frames_absmax: bad argument");
-  PlanarView v{st, sc, sh, sw, T, C, H, W};
+  PlanarView v;
+  if (int rc = planar_frames(src, amax, st, sc, sh, sw, T, C, H, W, &v, "frames_absmax")) return rc;
   hipLaunchKernelGGL(frames_absmax_kernel, dim3(grid_for((long long)T * C * H * W, 256 * 8)), dim3(256), 0,
                      (hipStream_t)stream, src, v, amax);
   return check_launch("frames_absmax");
@@ -523,14 +532,11 @@ extern "C" int sfvos_frames_absmax(const float* src, int64_t st, int64_t sc, int
 extern "C" int sfvos_add_inplace(void* dst, const void* src, int dtype, int64_t n, sfvos_stream_t stream) {
   SFVOS_REQUIRE(dst && src && n > 0 && n % 8 == 0, "add_inplace: n must be a positive multiple of 8");
   SFVOS_REQUIRE((((size_t)dst | (size_t)src) & 15) == 0, "add_inplace: pointers must be 16-byte aligned");
-  const long long chunks = n / (dtype == SFVOS_BF16 ? 8 : 4);
-  hipStream_t s = (hipStream_t)stream;
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(add_inplace_kernel<SFVOS_F32>, dim3(grid_for(chunks, 256 * 4)), dim3(256), 0, s,
-                                 (char*)dst, (const char*)src, chunks),
-              hipLaunchKernelGGL(add_inplace_kernel<SFVOS_BF16>, dim3(grid_for(chunks, 256 * 4)), dim3(256), 0, s,
-                                 (char*)dst, (const char*)src, chunks));
-  return check_launch("add_inplace");
+  const long long chunks = n / (16 / elt_bytes(dtype));
+  return launch_dt(dtype, "add_inplace", [&](auto dt) {
+    hipLaunchKernelGGL(add_inplace_kernel<dt>, dim3(grid_for(chunks, 256 * 4)), dim3(256), 0, (hipStream_t)stream,
+                       (char*)dst, (const char*)src, chunks);
+  });
 }
 
 static int mse_table(const sfvos_mse_table* t, MseTab* m, bool need_grad, const char* what) {
@@ -599,17 +605,14 @@ extern "C" int sfvos_planar_to_ndhwc(const float* src, void* dst, int dtype, int
 extern "C" int sfvos_ndhwc_to_frames(const void* src, int dtype, float* dst, int64_t st, int64_t sc, int64_t sh,
                                      int64_t sw, int T, int C, int H, int W, int ld, int accumulate,
                                      sfvos_stream_t stream) {
-  SFVOS_REQUIRE(src && dst && T > 0 && C > 0 && H > 0 && W > 0 && ld >= C, "ndhwc_to_frames: bad argument");
-  SFVOS_REQUIRE(C % 8 == 0 && ld % 8 == 0, "ndhwc_to_frames: C and ld must be multiples of 8");
-  PlanarView v{st, sc, sh, sw, T, C, H, W};
+  PlanarView v;
+  if (int rc = planar_frames(dst, src, st, sc, sh, sw, T, C, H, W, &v, "ndhwc_to_frames")) return rc;
+  SFVOS_REQUIRE(ld >= C && C % 8 == 0 && ld % 8 == 0, "ndhwc_to_frames: C and ld must be multiples of 8, ld >= C");
   dim3 grid((unsigned)ceil_div64((int64_t)H * W, 64), (unsigned)ceil_div(C, 64), (unsigned)T);
-  hipStream_t s = (hipStream_t)stream;
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(from_ndhwc_kernel<SFVOS_F32>, grid, dim3(256), 0, s, (const char*)src, ld, dst, v,
-                                 accumulate),
-              hipLaunchKernelGGL(from_ndhwc_kernel<SFVOS_BF16>, grid, dim3(256), 0, s, (const char*)src, ld, dst, v,
-                                 accumulate));
-  return check_launch("ndhwc_to_frames");
+  return launch_dt(dtype, "ndhwc_to_frames", [&](auto dt) {
+    hipLaunchKernelGGL(from_ndhwc_kernel<dt>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)src, ld, dst, v,
+                       accumulate);
+  });
 }
 
 static int make_level_views(const sfvos_planar_level* levels, int n_levels, int T, int C, int tile_px, LevelViews* t,
@@ -650,11 +653,10 @@ extern "C" int sfvos_pyramid_to_frames(const void* src, int dtype, const sfvos_p
   int rc = make_level_views(levels, n_levels, T, C, 64, &t, &vec, "pyramid_to_frames");
   if (rc) return rc;
   dim3 grid((unsigned)t.blk_begin[SFVOS_MAX_LEVELS], (unsigned)ceil_div(C, 64), (unsigned)T);
-  hipStream_t s = (hipStream_t)stream;
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(from_ndhwc_multi_kernel<SFVOS_F32>, grid, dim3(256), 0, s, (const char*)src, ld, t, accumulate),
-              hipLaunchKernelGGL(from_ndhwc_multi_kernel<SFVOS_BF16>, grid, dim3(256), 0, s, (const char*)src, ld, t, accumulate));
-  return check_launch("pyramid_to_frames");
+  return launch_dt(dtype, "pyramid_to_frames", [&](auto dt) {
+    hipLaunchKernelGGL(from_ndhwc_multi_kernel<dt>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)src, ld, t,
+                       accumulate);
+  });
 }
 
 extern "C" int sfvos_frames_to_pyramid(const sfvos_planar_level* levels, int n_levels, void* dst, int dtype, int T, int C,
@@ -673,10 +675,9 @@ extern "C" int sfvos_frames_to_pyramid(const sfvos_planar_level* levels, int n_l
   rc = make_level_views(levels, n_levels, T, C, 64, &t, &vec, "frames_to_pyramid");
   if (rc) return rc;
   dim3 grid((unsigned)t.blk_begin[SFVOS_MAX_LEVELS], (unsigned)ceil_div(C, 64), (unsigned)T);
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(to_ndhwc_multi_kernel<SFVOS_F32>, grid, dim3(256), 0, s, t, (char*)dst, ld),
-              hipLaunchKernelGGL(to_ndhwc_multi_kernel<SFVOS_BF16>, grid, dim3(256), 0, s, t, (char*)dst, ld));
-  return check_launch("frames_to_pyramid");
+  return launch_dt(dtype, "frames_to_pyramid", [&](auto dt) {
+    hipLaunchKernelGGL(to_ndhwc_multi_kernel<dt>, grid, dim3(256), 0, s, t, (char*)dst, ld);
+  });
 }
 
 extern "C" int sfvos_ndhwc_to_planar(const void* src, int dtype, float* dst, int64_t M, int C, int ld,
@@ -686,39 +687,29 @@ extern "C" int sfvos_ndhwc_to_planar(const void* src, int dtype, float* dst, int
 }
 
 extern "C" size_t sfvos_packed_weight_bytes(int dtype, int c_out, int c_in, int kt, int taps) {
-  return (size_t)c_out * c_in * kt * taps * (dtype == SFVOS_BF16 ? 2 : 4);
+  return (size_t)c_out * c_in * kt * taps * elt_bytes(dtype);
 }
 
-static int pack_common(const float* w, void* packed, int dtype, int c_out, int c_in, int kt, int taps, bool dgrad,
-                       sfvos_stream_t stream) {
-  SFVOS_REQUIRE(w && packed, "pack_weights: null pointer");
+template <bool DGRAD>
+static int pack_common(const float* w, void* packed, int dtype, int c_out, int c_in, int kt, int taps,
+                       sfvos_stream_t stream, const char* what) {
+  SFVOS_REQUIRE(w && packed, "%s: null pointer", what);
   SFVOS_REQUIRE(c_out % 32 == 0 && c_in % 32 == 0 && kt >= 1 && (taps == 9 || taps == 1),
-                "pack_weights: unsupported shape (c_out %d c_in %d kt %d taps %d)", c_out, c_in, kt, taps);
-  const long long total = (long long)c_out * c_in * kt * taps;
-  const unsigned grid = grid_for(total, 256);
-  hipStream_t s = (hipStream_t)stream;
-  if (dgrad)
-    DT_DISPATCH(dtype,
-                hipLaunchKernelGGL((pack_weights_kernel<SFVOS_F32, true>), dim3(grid), dim3(256), 0, s, w,
-                                   (char*)packed, c_out, c_in, kt, taps),
-                hipLaunchKernelGGL((pack_weights_kernel<SFVOS_BF16, true>), dim3(grid), dim3(256), 0, s, w,
-                                   (char*)packed, c_out, c_in, kt, taps));
-  else
-    DT_DISPATCH(dtype,
-                hipLaunchKernelGGL((pack_weights_kernel<SFVOS_F32, false>), dim3(grid), dim3(256), 0, s, w,
-                                   (char*)packed, c_out, c_in, kt, taps),
-                hipLaunchKernelGGL((pack_weights_kernel<SFVOS_BF16, false>), dim3(grid), dim3(256), 0, s, w,
-                                   (char*)packed, c_out, c_in, kt, taps));
-  return check_launch("pack_weights");
+                "%s: unsupported shape (c_out %d c_in %d kt %d taps %d)", what, c_out, c_in, kt, taps);
+  const unsigned grid = grid_for((long long)c_out * c_in * kt * taps, 256);
+  return launch_dt(dtype, what, [&](auto dt) {
+    hipLaunchKernelGGL((pack_weights_kernel<dt, DGRAD>), dim3(grid), dim3(256), 0, (hipStream_t)stream, w,
+                       (char*)packed, c_out, c_in, kt, taps);
+  }, "pack_weights");
 }
 
 extern "C" int sfvos_pack_weights_fwd(const float* w, void* packed, int dtype, int c_out, int c_in, int kt, int taps,
                                       sfvos_stream_t stream) {
-  return pack_common(w, packed, dtype, c_out, c_in, kt, taps, false, stream);
+  return pack_common<false>(w, packed, dtype, c_out, c_in, kt, taps, stream, "pack_weights_fwd");
 }
 extern "C" int sfvos_pack_weights_dgrad(const float* w, void* packed, int dtype, int c_out, int c_in, int kt, int taps,
                                         sfvos_stream_t stream) {
-  return pack_common(w, packed, dtype, c_out, c_in, kt, taps, true, stream);
+  return pack_common<true>(w, packed, dtype, c_out, c_in, kt, taps, stream, "pack_weights_dgrad");
 }
 
 extern "C" int sfvos_pack_weights_batch(const sfvos_pack_item* items, int n, int dtype, sfvos_stream_t stream) {
@@ -744,11 +735,9 @@ extern "C" int sfvos_pack_weights_batch(const sfvos_pack_item* items, int n, int
     }
   }
   t.blk_begin[SFVOS_MAX_PACK_ITEMS] = (int)blk;
-  hipStream_t s = (hipStream_t)stream;
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(pack_weights_batch_kernel<SFVOS_F32>, dim3((unsigned)blk), dim3(256), 0, s, t),
-              hipLaunchKernelGGL(pack_weights_batch_kernel<SFVOS_BF16>, dim3((unsigned)blk), dim3(256), 0, s, t));
-  return check_launch("pack_weights_batch");
+  return launch_dt(dtype, "pack_weights_batch", [&](auto dt) {
+    hipLaunchKernelGGL(pack_weights_batch_kernel<dt>, dim3((unsigned)blk), dim3(256), 0, (hipStream_t)stream, t);
+  });
 }
 
 extern "C" int sfvos_mask_union(const float* masks, int n, int64_t hw, float threshold, unsigned char* out,

@@ -1,6 +1,8 @@
-// Helpers shared by the HBM-bound kernels (elementwise.hip, batchnorm.hip): 16-byte pack/unpack,
-// deterministic column sums, dtype dispatch.
+// Helpers shared by the HBM-bound kernels (elementwise.hip, batchnorm.hip, maskhead.hip, window_shift.hip): 16-byte
+// pack/unpack, deterministic column sums; on the host, the f32 / bf16 activation checks and dtype dispatch.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace sfvos {
@@ -84,11 +86,34 @@ static inline unsigned grid_for(long long work_items, int per_block, unsigned ca
   return (unsigned)g;
 }
 
-#define DT_DISPATCH(dtype, CALL_F32, CALL_BF16)  /* f32 / bf16 only */                    \
-  do {                                                             \
-    if ((dtype) == SFVOS_F32) { CALL_F32; }                        \
-    else if ((dtype) == SFVOS_BF16) { CALL_BF16; }                 \
-    else { sfvos::set_error("bad dtype %d", (int)(dtype)); return SFVOS_E_ARG; } \
-  } while (0)
+// Bytes per element of an f32 / bf16 operand; 16 / elt_bytes elements fill a 16-byte chunk.  The entry points refuse
+// every other dtype, except packed_weight_bytes, which sizes it as f32.
+static inline int elt_bytes(int dtype) { return dtype == SFVOS_BF16 ? 2 : 4; }
+
+// f32 / bf16 activations: C a multiple of 32 up to 256, two pitches of whole 16-byte chunks
+static inline int check_act(const char* what, int dtype, int C, int ld_a, int ld_b) {
+  const int ce = 16 / elt_bytes(dtype);
+  SFVOS_REQUIRE(dtype == SFVOS_F32 || dtype == SFVOS_BF16, "%s: bad dtype %d", what, dtype);
+  SFVOS_REQUIRE(C > 0 && C % 32 == 0 && C <= 256, "%s: C %d must be a multiple of 32, <= 256", what, C);
+  SFVOS_REQUIRE(ld_a >= C && ld_b >= C && ld_a % ce == 0 && ld_b % ce == 0,
+                "%s: pitches %d, %d must be >= C and multiples of %d", what, ld_a, ld_b, ce);
+  return SFVOS_OK;
+}
+
+// Launch of a kernel template over f32 / bf16: launch(dt) gets dt = std::integral_constant<int, SFVOS_F32 or
+// SFVOS_BF16>, which instantiates the kernel (`kern<dt>`).  Any other dtype is refused as "<what>: bad dtype"; a launch
+// error is reported under `kernel`, by default `what`.
+template <class F>
+static int launch_dt(int dtype, const char* what, F&& launch, const char* kernel = nullptr) {
+  if (dtype == SFVOS_F32)
+    launch(std::integral_constant<int, SFVOS_F32>());
+  else if (dtype == SFVOS_BF16)
+    launch(std::integral_constant<int, SFVOS_BF16>());
+  else {
+    set_error("%s: bad dtype %d", what, dtype);
+    return SFVOS_E_ARG;
+  }
+  return check_launch(kernel ? kernel : what);
+}
 
 }  // namespace sfvos

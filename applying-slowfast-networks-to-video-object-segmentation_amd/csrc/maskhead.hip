@@ -409,36 +409,39 @@ __global__ __launch_bounds__(256) void deconv2x2_wgrad_kernel(const char* __rest
     out[((long long)ci * c_out + co) * 4 + ab] = acc[e];
   }
 }
+
+// channels of the deconvs and their packers
+static int check_channels(int c_in, int c_out, const char* what) {
+  SFVOS_REQUIRE(c_in > 0 && c_out > 0 && c_in % 32 == 0 && c_out % 32 == 0,
+                "%s: channels must be positive multiples of 32 (c_in %d, c_out %d)", what, c_in, c_out);
+  return SFVOS_OK;
+}
 }  // namespace sfvos
 
 using namespace sfvos;
 
 extern "C" int sfvos_pack_deconv2x2(const float* w, void* packed, int dtype, int c_in, int c_out,
                                     sfvos_stream_t stream) {
-  SFVOS_REQUIRE(w && packed && c_in > 0 && c_out > 0 && c_in % 32 == 0 && c_out % 32 == 0,
-                "pack_deconv2x2: channels must be positive multiples of 32");
+  SFVOS_REQUIRE(w && packed, "pack_deconv2x2: null pointer");
+  if (int rc = check_channels(c_in, c_out, "pack_deconv2x2")) return rc;
   const unsigned grid = grid_for(4ll * c_in * c_out, 256);
-  hipStream_t s = (hipStream_t)stream;
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(pack_deconv_kernel<SFVOS_F32>, dim3(grid), dim3(256), 0, s, w, (char*)packed, c_in, c_out),
-              hipLaunchKernelGGL(pack_deconv_kernel<SFVOS_BF16>, dim3(grid), dim3(256), 0, s, w, (char*)packed, c_in, c_out));
-  return check_launch("pack_deconv2x2");
+  return launch_dt(dtype, "pack_deconv2x2", [&](auto dt) {
+    hipLaunchKernelGGL(pack_deconv_kernel<dt>, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, (char*)packed, c_in,
+                       c_out);
+  });
 }
 
 extern "C" int sfvos_deconv2x2_relu(const void* x, const void* w_packed, const float* bias, void* y, int dtype, int n,
                                     int h, int w, int c_in, int c_out, int relu, sfvos_stream_t stream) {
-  SFVOS_REQUIRE(x && w_packed && y && n > 0 && h > 0 && w > 0, "deconv2x2: bad argument");
-  SFVOS_REQUIRE(c_in % 32 == 0 && c_out % 32 == 0 && c_in > 0 && c_out > 0, "deconv2x2: channels must be multiples of 32");
+  SFVOS_REQUIRE(x && w_packed && y && n > 0 && h > 0 && w > 0, "deconv2x2_relu: bad argument");
+  if (int rc = check_channels(c_in, c_out, "deconv2x2_relu")) return rc;
   const long long M = (long long)n * h * w;
-  SFVOS_REQUIRE(M < (1ll << 31), "deconv2x2: too many positions");
+  SFVOS_REQUIRE(M < (1ll << 31), "deconv2x2_relu: too many positions");
   dim3 grid((unsigned)ceil_div64(M, 32), (unsigned)ceil_div(4 * c_out, 128));
-  hipStream_t s = (hipStream_t)stream;
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(deconv2x2_kernel<SFVOS_F32>, grid, dim3(256), 0, s, (const char*)x, (const char*)w_packed,
-                                 bias, (char*)y, (int)M, h, w, c_in, c_out, relu),
-              hipLaunchKernelGGL(deconv2x2_kernel<SFVOS_BF16>, grid, dim3(256), 0, s, (const char*)x, (const char*)w_packed,
-                                 bias, (char*)y, (int)M, h, w, c_in, c_out, relu));
-  return check_launch("deconv2x2");
+  return launch_dt(dtype, "deconv2x2_relu", [&](auto dt) {
+    hipLaunchKernelGGL(deconv2x2_kernel<dt>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)x,
+                       (const char*)w_packed, bias, (char*)y, (int)M, h, w, c_in, c_out, relu);
+  }, "deconv2x2");
 }
 
 extern "C" int sfvos_mask_logits(const void* x, int dtype, const float* w, const float* bias, const int64_t* labels,
@@ -448,13 +451,10 @@ extern "C" int sfvos_mask_logits(const void* x, int dtype, const float* w, const
                 "mask_logits: bad argument");
   SFVOS_REQUIRE(!prob || labels || num_classes == 1, "mask_logits: prob needs the labels of the boxes");
   const long long pix = (long long)n * positions;
-  hipStream_t s = (hipStream_t)stream;
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(mask_logits_kernel<SFVOS_F32>, dim3((unsigned)ceil_div64(pix, 4)), dim3(256), 0, s,
-                                 (const char*)x, w, bias, (const long long*)labels, n, positions, c, num_classes, logits, prob),
-              hipLaunchKernelGGL(mask_logits_kernel<SFVOS_BF16>, dim3((unsigned)ceil_div64(pix, 4)), dim3(256), 0, s,
-                                 (const char*)x, w, bias, (const long long*)labels, n, positions, c, num_classes, logits, prob));
-  return check_launch("mask_logits");
+  return launch_dt(dtype, "mask_logits", [&](auto dt) {
+    hipLaunchKernelGGL(mask_logits_kernel<dt>, dim3((unsigned)ceil_div64(pix, 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const char*)x, w, bias, (const long long*)labels, n, positions, c, num_classes, logits, prob);
+  });
 }
 
 extern "C" int sfvos_paste_masks(const float* masks, const float* boxes, int n, int mask_size, int padding, int img_h,
@@ -471,17 +471,14 @@ extern "C" int sfvos_relu_bwd_rows(int64_t m) { return m > 0 ? (int)ceil_div64(m
 extern "C" int sfvos_relu_bwd(const void* dy, const void* a, void* dz, int dtype, int64_t m, int c, float* col_part,
                               sfvos_stream_t stream) {
   SFVOS_REQUIRE(dy && m > 0 && (dz || col_part), "relu_bwd: bad argument");
-  const int ce = dtype == SFVOS_BF16 ? 8 : 4;
+  const int ce = 16 / elt_bytes(dtype);
   SFVOS_REQUIRE(c > 0 && c % ce == 0 && c / ce <= 64 && 256 % (c / ce) == 0,
                 "relu_bwd: C must be a power-of-two number (<= 64) of 16-byte chunks");
   const unsigned grid = (unsigned)ceil_div64(m, RB_ROWS);
-  hipStream_t s = (hipStream_t)stream;
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(relu_bwd_kernel<SFVOS_F32>, dim3(grid), dim3(256), 0, s, (const char*)dy, (const char*)a,
-                                 (char*)dz, (long long)m, c, col_part),
-              hipLaunchKernelGGL(relu_bwd_kernel<SFVOS_BF16>, dim3(grid), dim3(256), 0, s, (const char*)dy, (const char*)a,
-                                 (char*)dz, (long long)m, c, col_part));
-  return check_launch("relu_bwd");
+  return launch_dt(dtype, "relu_bwd", [&](auto dt) {
+    hipLaunchKernelGGL(relu_bwd_kernel<dt>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const char*)dy,
+                       (const char*)a, (char*)dz, (long long)m, c, col_part);
+  });
 }
 
 extern "C" int sfvos_mask_bce_loss(const float* logits, const int64_t* labels, const float* targets, int n,
@@ -515,41 +512,34 @@ extern "C" int sfvos_mask_logits_bwd(const void* y, int dtype, const float* dlog
                 "mask_logits_bwd: C must be a multiple of 64 (<= %d), num_classes <= %d", 64 * MLB_MAXQ, MLB_MAXK);
   const unsigned grid = (unsigned)ceil_div64((long long)n * positions, MLB_PIX);
   const int lds = 4 * (num_classes * c + num_classes + c) * (int)sizeof(float);
-  hipStream_t s = (hipStream_t)stream;
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(mask_logits_bwd_kernel<SFVOS_F32>, dim3(grid), dim3(256), lds, s, (const char*)y, dlogits,
-                                 w, n, positions, c, num_classes, relu, (char*)dz, part),
-              hipLaunchKernelGGL(mask_logits_bwd_kernel<SFVOS_BF16>, dim3(grid), dim3(256), lds, s, (const char*)y, dlogits,
-                                 w, n, positions, c, num_classes, relu, (char*)dz, part));
-  return check_launch("mask_logits_bwd");
+  return launch_dt(dtype, "mask_logits_bwd", [&](auto dt) {
+    hipLaunchKernelGGL(mask_logits_bwd_kernel<dt>, dim3(grid), dim3(256), lds, (hipStream_t)stream, (const char*)y,
+                       dlogits, w, n, positions, c, num_classes, relu, (char*)dz, part);
+  });
 }
 
 extern "C" int sfvos_pack_deconv2x2_dgrad(const float* w, void* packed, int dtype, int c_in, int c_out,
                                           sfvos_stream_t stream) {
-  SFVOS_REQUIRE(w && packed && c_in > 0 && c_out > 0 && c_in % 32 == 0 && c_out % 32 == 0,
-                "pack_deconv2x2_dgrad: channels must be positive multiples of 32");
+  SFVOS_REQUIRE(w && packed, "pack_deconv2x2_dgrad: null pointer");
+  if (int rc = check_channels(c_in, c_out, "pack_deconv2x2_dgrad")) return rc;
   const unsigned grid = grid_for(4ll * c_in * c_out, 256);
-  hipStream_t s = (hipStream_t)stream;
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(pack_deconv_dgrad_kernel<SFVOS_F32>, dim3(grid), dim3(256), 0, s, w, (char*)packed, c_in, c_out),
-              hipLaunchKernelGGL(pack_deconv_dgrad_kernel<SFVOS_BF16>, dim3(grid), dim3(256), 0, s, w, (char*)packed, c_in, c_out));
-  return check_launch("pack_deconv2x2_dgrad");
+  return launch_dt(dtype, "pack_deconv2x2_dgrad", [&](auto dt) {
+    hipLaunchKernelGGL(pack_deconv_dgrad_kernel<dt>, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, (char*)packed,
+                       c_in, c_out);
+  });
 }
 
 extern "C" int sfvos_deconv2x2_dgrad(const void* dz, const void* w_packed, void* dx, int dtype, int n, int h, int w,
                                      int c_in, int c_out, sfvos_stream_t stream) {
   SFVOS_REQUIRE(dz && w_packed && dx && n > 0 && h > 0 && w > 0, "deconv2x2_dgrad: bad argument");
-  SFVOS_REQUIRE(c_in % 32 == 0 && c_out % 32 == 0 && c_in > 0 && c_out > 0, "deconv2x2_dgrad: channels must be multiples of 32");
+  if (int rc = check_channels(c_in, c_out, "deconv2x2_dgrad")) return rc;
   const long long M = (long long)n * h * w;
   SFVOS_REQUIRE(M < (1ll << 29), "deconv2x2_dgrad: too many positions");
   dim3 grid((unsigned)ceil_div64(M, 32), (unsigned)ceil_div(c_in, 128));
-  hipStream_t s = (hipStream_t)stream;
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(deconv2x2_dgrad_kernel<SFVOS_F32>, grid, dim3(256), 0, s, (const char*)dz,
-                                 (const char*)w_packed, (char*)dx, (int)M, h, w, c_in, c_out),
-              hipLaunchKernelGGL(deconv2x2_dgrad_kernel<SFVOS_BF16>, grid, dim3(256), 0, s, (const char*)dz,
-                                 (const char*)w_packed, (char*)dx, (int)M, h, w, c_in, c_out));
-  return check_launch("deconv2x2_dgrad");
+  return launch_dt(dtype, "deconv2x2_dgrad", [&](auto dt) {
+    hipLaunchKernelGGL(deconv2x2_dgrad_kernel<dt>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)dz,
+                       (const char*)w_packed, (char*)dx, (int)M, h, w, c_in, c_out);
+  });
 }
 
 static int deconv_wgrad_splits(long long M) {
@@ -565,21 +555,18 @@ extern "C" size_t sfvos_deconv2x2_wgrad_workspace_bytes(int n, int h, int w, int
 extern "C" int sfvos_deconv2x2_wgrad(const void* x, const void* dz, int dtype, int n, int h, int w, int c_in, int c_out,
                                      float* grad_w, int accumulate, void* workspace, sfvos_stream_t stream) {
   SFVOS_REQUIRE(x && dz && grad_w && workspace && n > 0 && h > 0 && w > 0, "deconv2x2_wgrad: bad argument");
-  SFVOS_REQUIRE(c_in % 32 == 0 && c_out % 32 == 0 && c_in > 0 && c_out > 0, "deconv2x2_wgrad: channels must be multiples of 32");
+  if (int rc = check_channels(c_in, c_out, "deconv2x2_wgrad")) return rc;
   const long long M = (long long)n * h * w;
   SFVOS_REQUIRE(M < (1ll << 29), "deconv2x2_wgrad: too many positions");
   const int splits = deconv_wgrad_splits(M);
   int per_split = (int)ceil_div64(M, splits);
   per_split = (per_split + 1) & ~1;  // whole k-pairs
   const int tiles = (c_in / 32) * 4 * (c_out / 32);
-  hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)ceil_div(tiles, 4), (unsigned)splits);
-  DT_DISPATCH(dtype,
-              hipLaunchKernelGGL(deconv2x2_wgrad_kernel<SFVOS_F32>, grid, dim3(256), 0, s, (const char*)x, (const char*)dz,
-                                 (float*)workspace, (int)M, h, w, c_in, c_out, per_split),
-              hipLaunchKernelGGL(deconv2x2_wgrad_kernel<SFVOS_BF16>, grid, dim3(256), 0, s, (const char*)x, (const char*)dz,
-                                 (float*)workspace, (int)M, h, w, c_in, c_out, per_split));
-  int rc = check_launch("deconv2x2_wgrad");
+  int rc = launch_dt(dtype, "deconv2x2_wgrad", [&](auto dt) {
+    hipLaunchKernelGGL(deconv2x2_wgrad_kernel<dt>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)x,
+                       (const char*)dz, (float*)workspace, (int)M, h, w, c_in, c_out, per_split);
+  });
   if (rc) return rc;
   return sfvos_reduce_rows((const float*)workspace, splits, c_in * c_out * 4, grad_w, accumulate, stream);
 }

@@ -129,18 +129,6 @@ __global__ __launch_bounds__(WS_THREADS) void shift_frames_kernel(const char* __
   }
 }
 
-template <int DT>
-static void launch_shift(const void* prev, const void* fresh, void* out, const ShiftTab& tab, int C, int ld,
-                         float* part, hipStream_t st) {
-  const dim3 grid((unsigned)tab.blk_begin[SFVOS_MAX_LEVELS]);
-  if (part)
-    hipLaunchKernelGGL((shift_frames_kernel<DT, true>), grid, dim3(WS_THREADS), 0, st, (const char*)prev,
-                       (const char*)fresh, (char*)out, tab, C, ld, part);
-  else
-    hipLaunchKernelGGL((shift_frames_kernel<DT, false>), grid, dim3(WS_THREADS), 0, st, (const char*)prev,
-                       (const char*)fresh, (char*)out, tab, C, ld, part);
-}
-
 static bool overlaps(const void* a, long long a_bytes, const void* b, long long b_bytes) {
   const char *pa = (const char*)a, *pb = (const char*)b;
   return pa < pb + b_bytes && pb < pa + a_bytes;
@@ -164,19 +152,23 @@ extern "C" int sfvos_shift_frames(const void* prev, const void* fresh, void* out
   ShiftTab tab;
   int rc = make_shift_tab(pyr, B, T, s, C, &tab, "shift_frames");
   if (rc) return rc;
-  SFVOS_REQUIRE(dtype == SFVOS_F32 || dtype == SFVOS_BF16, "shift_frames: dtype must be f32 or bf16");
-  const int ce = dtype == SFVOS_BF16 ? 8 : 4, es = dtype == SFVOS_BF16 ? 2 : 4;
-  SFVOS_REQUIRE(ld >= C && ld % ce == 0, "shift_frames: pitch %d must be >= C and a multiple of %d", ld, ce);
+  if ((rc = check_act("shift_frames", dtype, C, ld, ld))) return rc;
   SFVOS_REQUIRE(prev && fresh && out, "shift_frames: null buffer");
   SFVOS_REQUIRE(((uintptr_t)prev | (uintptr_t)fresh | (uintptr_t)out | (uintptr_t)stat_part) % 16 == 0,
                 "shift_frames: buffers must be 16-byte aligned");
+  const int es = elt_bytes(dtype);
   const long long b_out = tab.m_out * ld * es, b_fresh = tab.m_fresh * ld * es;
   SFVOS_REQUIRE(!overlaps(out, b_out, prev, b_out) && !overlaps(out, b_out, fresh, b_fresh),
                 "shift_frames: out must not overlap prev or fresh (never in place)");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SFVOS_F32)
-    launch_shift<SFVOS_F32>(prev, fresh, out, tab, C, ld, stat_part, st);
-  else
-    launch_shift<SFVOS_BF16>(prev, fresh, out, tab, C, ld, stat_part, st);
-  return check_launch("shift_frames");
+  auto launch = [&](auto dt, auto stats) {
+    hipLaunchKernelGGL((shift_frames_kernel<dt, stats>), dim3((unsigned)tab.blk_begin[SFVOS_MAX_LEVELS]),
+                       dim3(WS_THREADS), 0, (hipStream_t)stream, (const char*)prev, (const char*)fresh, (char*)out, tab,
+                       C, ld, stat_part);
+  };
+  return launch_dt(dtype, "shift_frames", [&](auto dt) {
+    if (stat_part)
+      launch(dt, std::true_type());
+    else
+      launch(dt, std::false_type());
+  });
 }
