@@ -512,10 +512,18 @@ extern "C" int sfvos_mask_logits_bwd(const void* y, int dtype, const float* dlog
                 "mask_logits_bwd: C must be a multiple of 64 (<= %d), num_classes <= %d", 64 * MLB_MAXQ, MLB_MAXK);
   const unsigned grid = (unsigned)ceil_div64((long long)n * positions, MLB_PIX);
   const int lds = 4 * (num_classes * c + num_classes + c) * (int)sizeof(float);
-  return launch_dt(dtype, "mask_logits_bwd", [&](auto dt) {
+  // c = 512 with 7 or 8 classes needs 65 648 / 73 856 bytes, above the 64 KB a kernel gets by default: the limit is
+  // raised once per (kernel instance, device) to what the largest admitted shape needs
+  constexpr int lds_max = 4 * (MLB_MAXK * 64 * MLB_MAXQ + MLB_MAXK + 64 * MLB_MAXQ) * (int)sizeof(float);
+  int attr_rc = SFVOS_OK;
+  const int rc = launch_dt(dtype, "mask_logits_bwd", [&](auto dt) {
+    static LdsAttrOnce once;
+    attr_rc = once.ensure((const void*)mask_logits_bwd_kernel<dt>, lds_max, "mask_logits_bwd");
+    if (attr_rc) return;
     hipLaunchKernelGGL(mask_logits_bwd_kernel<dt>, dim3(grid), dim3(256), lds, (hipStream_t)stream, (const char*)y,
                        dlogits, w, n, positions, c, num_classes, relu, (char*)dz, part);
   });
+  return attr_rc ? attr_rc : rc;
 }
 
 extern "C" int sfvos_pack_deconv2x2_dgrad(const float* w, void* packed, int dtype, int c_in, int c_out,

@@ -94,6 +94,11 @@ CONV_CASES = [
     # a padded 32-px tile, 10 and 5 are tall tiles only; 4-, 2- and 1-frame blocks (t_out 7 = 4 + 2 + 1)
     (1, 9, [(24, 42), (17, 48), (12, 21)], 256, 32, 3, 9),
     (2, 8, [(40, 10), (3, 5)], 32, 32, 2, 9),
+    # the 3x3 convs of the mask head: one frame (kt = t_in = 1), batch = RoIs, one 14x14 or 7x7 level
+    (1, 1, [(14, 14)], 256, 256, 1, 9),
+    (9, 1, [(14, 14)], 256, 256, 1, 9),
+    (33, 1, [(7, 7)], 256, 256, 1, 9),
+    (33, 1, [(14, 14)], 256, 32, 1, 9),
 ]
 
 
@@ -243,7 +248,10 @@ def test_conv3d_window_beyond_the_buffer_reads_zero_frames(lib, prec, case):
                                   (1, 22, [(12, 21), (3, 3)], 32, 64, 21, 1), (2, 41, [(6, 7)], 32, 64, 40, 1),
                                   (1, 43, [(4, 9)], 32, 64, 42, 1),
                                   # fast_conv3's shape (all frames -> one): single-frame blocks, one temporal tap each
-                                  (2, 12, [(9, 37), (4, 5)], 32, 32, 12, 9)])
+                                  (2, 12, [(9, 37), (4, 5)], 32, 32, 12, 9),
+                                  # the 3x3 convs of the mask head (kt = t_in = 1, batch = RoIs)
+                                  (9, 1, [(14, 14)], 256, 256, 1, 9), (33, 1, [(7, 7)], 256, 32, 1, 9),
+                                  (1, 1, [(7, 7)], 256, 256, 1, 9)])
 def test_conv3d_dgrad_and_accumulate(lib, prec, case):
     B, T, shapes, cin, cout, kt, taps = case
     g = torch.Generator().manual_seed(99)
@@ -333,6 +341,10 @@ WGRAD_CASES = [
     (1, 6, [(21, 19), (40, 10)], 32, 32, 3, 9),    # the same, levels taller than the 16-row tile: both row halves live, 3 of 4 taps
     (1, 9, [(18, 16)], 32, 64, 5, 1),              # cfg (2,1,4) lateral
     (1, 24, [(5, 33), (2, 2)], 32, 64, 20, 1),
+    # the 3x3 convs of the mask head (kt = t_in = 1, batch = RoIs)
+    (1, 1, [(14, 14)], 256, 256, 1, 9),
+    (9, 1, [(14, 14)], 256, 256, 1, 9),
+    (33, 1, [(7, 7)], 256, 32, 1, 9),
 ]
 
 
