@@ -12,10 +12,13 @@ from .stream import SlowFastStream  # noqa: F401
 from .windows import SlowFastWindows  # noqa: F401
 from .mask_head import (MaskBranch, MaskRCNNHeads, MaskRCNNPredictor, maskrcnn_inference,  # noqa: F401
                         maskrcnn_loss, paste_masks_in_image)
+from .box_head import (BoxBranch, FastRCNNPredictor, RoIHeadsInference, TwoMLPHead, decode_boxes,  # noqa: F401
+                       encode_boxes, fastrcnn_loss, resize_boxes)
 from .parallel import GradBucket, init_distributed  # noqa: F401
 from .roi_align import MultiScaleRoIAlign, roi_align  # noqa: F401
 from .graph import GraphedStep  # noqa: F401
 
 __all__ = ['SlowFastLayers', 'PackedClip', 'SlowFastPlan', 'FusedSGD', 'GradBucket', 'init_distributed',
            'MSEProxyLoss', 'calc_kernel_sizes', 'calc_fuse_kernel_size', 'davis_pyramid', 'union_mask', 'SlowFastStream', 'SlowFastWindows', 'MaskBranch', 'MaskRCNNHeads', 'MaskRCNNPredictor',
-           'maskrcnn_inference', 'maskrcnn_loss', 'paste_masks_in_image', 'MultiScaleRoIAlign', 'roi_align', 'GraphedStep']
+           'maskrcnn_inference', 'maskrcnn_loss', 'paste_masks_in_image', 'MultiScaleRoIAlign', 'roi_align', 'GraphedStep', 'BoxBranch', 'TwoMLPHead', 'FastRCNNPredictor',
+           'RoIHeadsInference', 'fastrcnn_loss', 'encode_boxes', 'decode_boxes', 'resize_boxes']

@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SFVOS_LIB') or os.path.join(_HERE, 'csrc', 'libsfvos.so')  # SFVOS_LIB: A/B builds
 
 F32, BF16, FP8 = 0, 1, 2
-ABI_REVISION = 301   # the revision of include/sfvos.h this binding mirrors
+ABI_REVISION = 302   # the revision of include/sfvos.h this binding mirrors
 MAX_LEVELS = 8
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -146,6 +146,24 @@ SIGNATURES = {
     'sfvos_roi_align_workspace_bytes': (C.c_size_t, [i32]),
     'sfvos_roi_align': (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, f32, i32, i32, vp, vp, vp]),
     'sfvos_roi_align_bwd': (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, f32, i32, i32, vp, vp, i32, vp]),
+    'sfvos_pack_dense_fwd': (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    'sfvos_pack_dense_dgrad': (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    'sfvos_dense_splits': (i32, [i32, i32, i32, i32]),
+    'sfvos_dense_workspace_bytes': (C.c_size_t, [i32, i32, i32, i32]),
+    'sfvos_dense': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+    'sfvos_dense_wgrad': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp]),
+    'sfvos_relu_bwd_wide_rows': (i32, [i32]),
+    'sfvos_relu_bwd_wide': (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
+    'sfvos_box_predictor': (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    'sfvos_box_predictor_bwd_rows': (i32, [i32]),
+    'sfvos_box_predictor_bwd': (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    'sfvos_fastrcnn_loss': (i32, [vp, vp, vp, vp, i32, i32, f32, vp, vp]),
+    'sfvos_fastrcnn_loss_grad': (i32, [vp, vp, vp, vp, vp, i32, i32, f32, vp, vp, vp]),
+    'sfvos_box_decode': (i32, [vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, f32, f32, vp, vp, vp, vp]),
+    'sfvos_box_encode': (i32, [vp, vp, i32, f32, f32, f32, f32, vp, vp]),
+    'sfvos_box_scale': (i32, [vp, i32, f32, f32, vp, vp]),
+    'sfvos_detections_workspace_bytes': (C.c_size_t, [i32]),
+    'sfvos_detections': (i32, [vp, vp, vp, i32, i32, f32, f32, f32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

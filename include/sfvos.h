@@ -67,7 +67,9 @@ typedef struct sfvos_levels {
  * sfvos_add_inplace, sfvos_mse_loss / _grad, mask-head entry points; 201 = sfvos_bn_running argument of the BN-apply
  * calls, mask-branch training entry points, sfvos_pack_weights_batch, sfvos_pyramid_to_frames / sfvos_frames_to_pyramid;
  * 300 (round 3) = sfvos_roi_levels / sfvos_roi_align / sfvos_roi_align_bwd (+ workspace query); 301 =
- * sfvos_shift_frames / sfvos_shift_frames_stat_rows (first-layer reuse across consecutive training windows). */
+ * sfvos_shift_frames / sfvos_shift_frames_stat_rows (first-layer reuse across consecutive training windows); 302 = the
+ * box branch of roi_heads: sfvos_dense and its packers / gradients, sfvos_box_predictor, sfvos_fastrcnn_loss,
+ * sfvos_box_decode / _encode, sfvos_detections. */
 int sfvos_version(void);
 /* sizes[0..n) = sizeof(sfvos_conv_desc), sizeof(sfvos_pyramid), sizeof(sfvos_levels), sizeof(sfvos_mse_table),
  * sizeof(sfvos_bn_running), sizeof(sfvos_pack_item), sizeof(sfvos_planar_level) as THIS library was compiled; returns
@@ -452,6 +454,89 @@ int sfvos_deconv2x2_dgrad(const void* dz, const void* w_packed, void* dx, int dt
 size_t sfvos_deconv2x2_wgrad_workspace_bytes(int n, int h, int w, int c_in, int c_out);
 int sfvos_deconv2x2_wgrad(const void* x, const void* dz, int dtype, int n, int h, int w, int c_in, int c_out,
                           float* grad_w, int accumulate, void* workspace, sfvos_stream_t stream);
+
+/* ---- box branch of roi_heads (model.py:346: box_roi_pool -> box_head = TwoMLPHead(12544, 1024) -> box_predictor =
+ * FastRCNNPredictor(1024, 2) -> fastrcnn_loss | postprocess_detections; model.py:347: transform.postprocess resizes the
+ * boxes).  torchvision's arithmetic, restated from its published sources (parity unpinned by the reference: torchvision
+ * is neither vendored nor installed).  No atomics on data: every result is bit-identical from run to run. ---- */
+
+/* Dense layer y[m][n] = act(x[m][k] . W^T + bias): x, y row-major `dtype`, w_packed the image sfvos_pack_dense_fwd makes
+ * of nn.Linear's weight [n_out][k_in] fp32; act = ReLU when relu != 0; bias (fp32, may be NULL).  n and k: multiples of
+ * 32.  The same call with the image of sfvos_pack_dense_dgrad (sizes swapped: n = k_in, k = n_out), bias NULL, relu 0 is
+ * the data gradient dx[m][k_in] = dz[m][n_out] . W.  positions (HW) > 1: the k_in columns of the state-dict weight are
+ * (c, p)-ordered (torchvision flattens NCHW RoI features, column c*HW + p) while the rows of x / dx are channels-last
+ * (column p*C + c, C = k_in / HW); the images carry that permutation.  fc6: positions = 49.
+ * K is split into sfvos_dense_splits(dtype, m, n, k) fp32 slabs in `workspace` (sfvos_dense_workspace_bytes, may be
+ * NULL when that is 0), summed in a fixed order by a second launch that applies bias, ReLU and the store's rounding. */
+int sfvos_pack_dense_fwd(const float* w, void* packed, int dtype, int n_out, int k_in, int positions,
+                         sfvos_stream_t stream);
+int sfvos_pack_dense_dgrad(const float* w, void* packed, int dtype, int n_out, int k_in, int positions,
+                           sfvos_stream_t stream);
+int sfvos_dense_splits(int dtype, int m, int n, int k);
+size_t sfvos_dense_workspace_bytes(int dtype, int m, int n, int k);
+int sfvos_dense(const void* x, const void* w_packed, const float* bias, void* y, int dtype, int m, int n, int k, int relu,
+                void* workspace, sfvos_stream_t stream);
+/* grad_w[n][k] (fp32, state-dict layout and column order) (=|+=) sum_m dz[m][n] x[m][k']; x [m][k] (channels-last
+ * columns when positions > 1), dz [m][n], both `dtype`; one exact-f32 MFMA chain over the m rows per output. */
+int sfvos_dense_wgrad(const void* x, const void* dz, int dtype, int m, int n, int k, int positions, float* grad_w,
+                      int accumulate, sfvos_stream_t stream);
+/* sfvos_relu_bwd for rows of any width: dz[m][c] = a[m][c] > 0 ? dy[m][c] : 0 (a == NULL: dz = dy; dz may alias dy or be
+ * NULL); col_part (may be NULL): sfvos_relu_bwd_wide_rows(m) rows of [c] fp32 column sums over 64 rows each. */
+int sfvos_relu_bwd_wide_rows(int m);
+int sfvos_relu_bwd_wide(const void* dy, const void* a, void* dz, int dtype, int m, int c, float* col_part,
+                        sfvos_stream_t stream);
+
+/* FastRCNNPredictor: logits[m][num_classes] = x . w_cls^T + b_cls, deltas[m][4 num_classes] = x . w_box^T + b_box;
+ * x [m][c] `dtype`, weights and outputs fp32; num_classes <= 8. */
+int sfvos_box_predictor(const void* x, int dtype, const float* w_cls, const float* b_cls, const float* w_box,
+                        const float* b_box, int m, int c, int num_classes, float* logits, float* deltas,
+                        sfvos_stream_t stream);
+/* Its backward and that of the ReLU that produced x (relu != 0): with g = (dlogits | ddeltas) [m][J], J = 5 num_classes,
+ * w = (w_cls | w_box) [J][c]:  dz[m][c] = (relu == 0 || x > 0) ? sum_j g[m][j] w[j][c] : 0  (`dtype`);
+ * part: sfvos_box_predictor_bwd_rows(m) rows of [J*c + J + c] fp32 = (grad of w | grad of the biases | column sums of
+ * dz = bias gradient of the layer that produced x) over 64 rows each (sfvos_reduce_rows). */
+int sfvos_box_predictor_bwd_rows(int m);
+int sfvos_box_predictor_bwd(const void* x, int dtype, const float* dlogits, const float* ddeltas, const float* w_cls,
+                            const float* w_box, int m, int c, int num_classes, int relu, void* dz, float* part,
+                            sfvos_stream_t stream);
+
+/* roi_heads.fastrcnn_loss on the n sampled RoIs: losses[0] = mean cross_entropy(logits [n][K], labels),
+ * losses[1] = sum over the RoIs with label > 0 of smooth_l1(deltas[i][4 label .. +3] - targets[i][0..3], beta) / n
+ * (torchvision: beta = 1/9); fixed-order f64 reduction.  A label outside [0, K) makes both losses NaN and its rows of
+ * the gradient zero; nothing is read through it.  upstream: two device floats (grad of the two losses) or NULL for 1. */
+int sfvos_fastrcnn_loss(const float* logits, const float* deltas, const int64_t* labels, const float* targets, int n,
+                        int num_classes, float beta, float* losses, sfvos_stream_t stream);
+int sfvos_fastrcnn_loss_grad(const float* logits, const float* deltas, const int64_t* labels, const float* targets,
+                             const float* upstream, int n, int num_classes, float beta, float* dlogits, float* ddeltas,
+                             sfvos_stream_t stream);
+
+/* BoxCoder.decode of the classes [first_class, K) of each of the m RoIs (deltas [m][4K], proposals [m][4], weights
+ * (wx, wy, ww, wh), dw / dh clamped at `clip`), clipped to the image when img_w > 0: boxes [m (K - first_class)][4];
+ * scores (may be NULL; needs logits [m][K]) = softmax probability of the class, labels (may be NULL) = the class.
+ * postprocess_detections: first_class = 1, weights (10, 10, 5, 5), clip = log(1000 / 16). */
+int sfvos_box_decode(const float* logits, const float* deltas, const float* proposals, int m, int num_classes,
+                     int first_class, float wx, float wy, float ww, float wh, float clip, float img_h, float img_w,
+                     float* boxes, float* scores, int64_t* labels, sfvos_stream_t stream);
+/* BoxCoder.encode_single: targets[m][4] of the reference boxes [m][4] against the proposals [m][4]. */
+int sfvos_box_encode(const float* reference, const float* proposals, int m, float wx, float wy, float ww, float wh,
+                     float* targets, sfvos_stream_t stream);
+
+/* transform.resize_boxes: out[i] = (x1 ratio_w, y1 ratio_h, x2 ratio_w, y2 ratio_h) of boxes[i], n boxes. */
+int sfvos_box_scale(const float* boxes, int n, float ratio_h, float ratio_w, float* out, sfvos_stream_t stream);
+
+/* The rest of postprocess_detections on n candidates (boxes [n][4], scores [n], labels [n] int64): keep score >
+ * score_thresh and both sides >= min_size, rank by descending score (ties: the lower index first), greedy NMS at IoU >
+ * nms_thresh among candidates of the same label (batched_nms), the first max_det survivors.  count[0] = their number d;
+ * out_* hold max_det entries, the first d in descending score: boxes (x scaled by ratio_w, y by ratio_h: resize_boxes),
+ * scores, labels, out_index = the candidate's index, out_roi = out_index / classes_per_roi (the RoI it came from);
+ * entries behind d are 0 / -1.  Meant for the few thousand candidates of one image (1000 proposals x (K - 1) classes): the
+ * ranking counts over all pairs (n^2 steps) and the masks take n^2 / 8 bytes, so n <= 8192 and larger sets are refused;
+ * workspace: sfvos_detections_workspace_bytes(n) (0 for a refused n). */
+size_t sfvos_detections_workspace_bytes(int n);
+int sfvos_detections(const float* boxes, const float* scores, const int64_t* labels, int n, int classes_per_roi,
+                     float score_thresh, float min_size, float nms_thresh, int max_det, float ratio_h, float ratio_w,
+                     void* workspace, int* count, float* out_boxes, float* out_scores, int64_t* out_labels,
+                     int* out_index, int* out_roi, sfvos_stream_t stream);
 
 /* ---- evaluation-side reducer (reference code/helpers/davis_evaluate.py:40-42) ------------ */
 
