@@ -20,7 +20,8 @@ import torch
 from torch import nn
 
 from . import _lib
-from .mask_head import MaskBranch, _check_gpu, _to_nhwc, _to_nchw
+from ._heads import _check_gpu, _check_precision, _f32, _pack, _project_bwd, _reduce_rows, _to_nchw, _to_nhwc
+from .mask_head import MaskBranch
 from .module import _DT, _ptr, _stream
 from .roi_align import MultiScaleRoIAlign
 
@@ -30,24 +31,10 @@ SMOOTH_L1_BETA = 1.0 / 9
 MIN_BOX_SIZE = 1e-2
 
 
-def _f32(t, dev=None):
-    t = t.detach()
-    if dev is not None and t.device != dev:
-        t = t.to(dev)
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
-
-
 def _inference_only(module, x):
     if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters())):
         raise RuntimeError('%s.forward on its own is inference only (call it under torch.no_grad()); '
                            'BoxBranch.forward is the differentiable path' % type(module).__name__)
-
-
-def _pack_dense(fn, w, dt_id, tdt, positions):
-    wc = _f32(w)
-    packed = torch.empty(wc.numel(), dtype=tdt, device=w.device)
-    _lib.call(fn, _ptr(wc), _ptr(packed), dt_id, wc.shape[0], wc.shape[1], positions, _stream())
-    return packed
 
 
 def _dense(x, image, bias, dt_id, tdt, n, relu):
@@ -61,12 +48,6 @@ def _dense(x, image, bias, dt_id, tdt, n, relu):
     return y
 
 
-def _reduce_rows(part):
-    out = torch.empty(part.shape[1], dtype=torch.float32, device=part.device)
-    _lib.call('sfvos_reduce_rows', _ptr(part), part.shape[0], part.shape[1], _ptr(out), 0, _stream())
-    return out
-
-
 class TwoMLPHead(nn.Module):
     """torchvision's TwoMLPHead(in_channels, representation_size): fc6, fc7, each followed by ReLU, on the flattened RoI
     features.  forward(x [N,C,H,W] fp32) -> [N,representation_size] fp32.  The kernels read the features channels-last;
@@ -75,17 +56,15 @@ class TwoMLPHead(nn.Module):
 
     def __init__(self, in_channels=12544, representation_size=1024, precision='fp32'):
         super(TwoMLPHead, self).__init__()
-        if precision not in ('fp32', 'bf16'):
-            raise ValueError("precision must be 'fp32' or 'bf16'")
-        self.precision = precision
+        self.precision = _check_precision(precision)
         self.fc6 = nn.Linear(in_channels, representation_size)
         self.fc7 = nn.Linear(representation_size, representation_size)
         self._images = _lib.WeightImages()
 
     def _packed(self, fc, dt_id, tdt, positions, dgrad=False):
         fn = 'sfvos_pack_dense_dgrad' if dgrad else 'sfvos_pack_dense_fwd'
-        return self._images.get((id(fc), fn, dt_id, positions), (fc.weight,), _pack_dense, fn, fc.weight, dt_id, tdt,
-                                positions)
+        return self._images.get((id(fc), fn, dt_id, positions), (fc.weight,), _pack, fn, fc.weight, dt_id, tdt,
+                                fc.out_features, fc.in_features, positions)
 
     def forward_rows(self, x):
         """x [N,C,H,W] -> (x rows [N,H*W*C] channels-last, h6, h7), all in the compute dtype."""
@@ -117,11 +96,9 @@ class FastRCNNPredictor(nn.Module):
 
     def __init__(self, in_channels=1024, num_classes=2, precision='fp32'):
         super(FastRCNNPredictor, self).__init__()
-        if precision not in ('fp32', 'bf16'):
-            raise ValueError("precision must be 'fp32' or 'bf16'")
+        self.precision = _check_precision(precision)
         if not 1 <= num_classes <= 8:
             raise ValueError('FastRCNNPredictor: 1..8 classes are implemented')
-        self.precision = precision
         self.cls_score = nn.Linear(in_channels, num_classes)
         self.bbox_pred = nn.Linear(in_channels, num_classes * 4)
 
@@ -172,17 +149,9 @@ class _BoxBranchFn(torch.autograd.Function):
         dl = _f32(dlogits) if dlogits is not None else torch.zeros((N, K), **f32)
         dd = _f32(ddeltas) if ddeltas is not None else torch.zeros((N, 4 * K), **f32)
         # ---- cls_score + bbox_pred and fc7's ReLU
-        J = 5 * K
-        prow = lib.sfvos_box_predictor_bwd_rows(N)
-        part = torch.empty((prow, J * R + J + R), **f32)
-        dz7 = torch.empty_like(h7)
-        wc, wb = _f32(pred.cls_score.weight), _f32(pred.bbox_pred.weight)
-        _lib.call('sfvos_box_predictor_bwd', _ptr(h7), dt_id, _ptr(dl), _ptr(dd), _ptr(wc), _ptr(wb), N, R, K, 1,
-                  _ptr(dz7), _ptr(part), _stream())
-        comb = _reduce_rows(part)
-        g_w = comb[:J * R].view(J, R)
-        g_b = comb[J * R:J * R + J]
-        g_b7 = comb[J * R + J:]
+        dz7, g_w, g_b, g_b7 = _project_bwd('sfvos_box_predictor_bwd', h7, dt_id,
+                                           (dl, dd, _f32(pred.cls_score.weight), _f32(pred.bbox_pred.weight)),
+                                           (N, R, K), lib.sfvos_box_predictor_bwd_rows(N), 5 * K)
         # ---- fc7
         R6 = head.fc6.out_features
         g_w7 = None

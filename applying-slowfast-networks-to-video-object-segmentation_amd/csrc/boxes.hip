@@ -3,7 +3,7 @@
 // postprocess_detections; _utils.py: BoxCoder; ops/boxes.py: clip_boxes_to_image, remove_small_boxes, batched_nms;
 // transform.py: resize_boxes) -- parity unpinned by the reference, torchvision is neither vendored nor installed:
 //
-//   cls_score (C -> K) + bbox_pred (C -> 4K)                       sfvos_box_predictor / _bwd
+//   cls_score (C -> K) + bbox_pred (C -> 4K)                       sfvos_box_predictor / _bwd (project.hip)
 //   cross_entropy + smooth_l1(beta 1/9, sum) / N                   sfvos_fastrcnn_loss / _grad
 //   BoxCoder.decode + softmax + clip, class 0 dropped              sfvos_box_decode;  BoxCoder.encode_single: sfvos_box_encode
 //   score threshold, small boxes, class-wise NMS, top k, resize    sfvos_detections
@@ -13,96 +13,9 @@
 
 namespace sfvos {
 
-constexpr int BP_MAXK = 8;   // classes
 // candidates of one sfvos_detections call: 1000 RoIs x 7 foreground classes fit; ranking is n^2 compare steps
 // (6.7e7 at the cap) and the IoU masks take n^2 / 8 bytes (8 MB)
 constexpr int DET_MAX_N = 8192;
-
-// ---- predictor: one wave per RoI row, fp32 weights ------------------------------------------------------------------
-//   logits[m][k] = b_cls[k] + sum_c x[m][c] w_cls[k][c];  deltas[m][j] = b_box[j] + sum_c x[m][c] w_box[j][c]
-template <int DT>
-__global__ __launch_bounds__(256) void box_predictor_kernel(const char* __restrict__ x, const float* __restrict__ w_cls,
-                                                            const float* __restrict__ b_cls,
-                                                            const float* __restrict__ w_box,
-                                                            const float* __restrict__ b_box, int M, int C, int K,
-                                                            float* logits, float* deltas) {
-  typedef typename Elt<DT>::type T;
-  const int lane = threadIdx.x & 63;
-  const int m = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (m >= M) return;
-  const T* xr = (const T*)x + (long long)m * C;
-  for (int j = 0; j < 5 * K; ++j) {
-    const float* w = j < K ? w_cls + (long long)j * C : w_box + (long long)(j - K) * C;
-    float s = 0.f;
-    for (int c = lane; c < C; c += 64) s += Elt<DT>::to_f32(xr[c]) * w[c];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) {
-      if (j < K)
-        logits[(long long)m * K + j] = s + (b_cls ? b_cls[j] : 0.f);
-      else
-        deltas[(long long)m * 4 * K + j - K] = s + (b_box ? b_box[j - K] : 0.f);
-    }
-  }
-}
-
-// ---- predictor backward and the ReLU in front of it -------------------------------------------------------------------
-// g[m][j] = (dlogits | ddeltas)[m][j], w[j][c] = (w_cls | w_box)[j][c], J = 5 K:
-//   dz[m][c] = (relu == 0 || x[m][c] > 0) ? sum_j g[m][j] w[j][c] : 0
-//   part[row block] = [ sum_m g[m][j] x[m][c]  (J x C) | sum_m g[m][j]  (J) | sum_m dz[m][c]  (C) ]  over BPB_ROWS rows
-// thread = one column c; the rows' g sit in LDS.
-constexpr int BPB_ROWS = 64;
-template <int DT, int JMAX>
-__global__ __launch_bounds__(256) void box_predictor_bwd_kernel(const char* __restrict__ x,
-                                                                const float* __restrict__ dlogits,
-                                                                const float* __restrict__ ddeltas,
-                                                                const float* __restrict__ w_cls,
-                                                                const float* __restrict__ w_box, int M, int C, int K,
-                                                                int relu, char* dz, float* part) {
-  typedef typename Elt<DT>::type T;
-  __shared__ float g[BPB_ROWS][JMAX];
-  const int J = 5 * K, L = J * C + J + C;
-  const int m0 = blockIdx.x * BPB_ROWS, rows = min(BPB_ROWS, M - m0);
-  for (int i = threadIdx.x; i < BPB_ROWS * JMAX; i += 256) {
-    const int r = i / JMAX, j = i - r * JMAX;
-    float v = 0.f;
-    if (r < rows && j < J) v = j < K ? dlogits[(long long)(m0 + r) * K + j] : ddeltas[(long long)(m0 + r) * 4 * K + j - K];
-    g[r][j] = v;
-  }
-  __syncthreads();
-  float* out = part + (long long)blockIdx.x * L;
-  const int c = blockIdx.y * 256 + threadIdx.x;
-  if (blockIdx.y == 0 && (int)threadIdx.x < J) {
-    float s = 0.f;
-    for (int r = 0; r < rows; ++r) s += g[r][threadIdx.x];
-    out[J * C + threadIdx.x] = s;
-  }
-  if (c >= C) return;
-  float aw[JMAX], wr[JMAX];
-#pragma unroll
-  for (int j = 0; j < JMAX; ++j) {
-    aw[j] = 0.f;
-    wr[j] = j < J ? (j < K ? w_cls[(long long)j * C + c] : w_box[(long long)(j - K) * C + c]) : 0.f;
-  }
-  float cs = 0.f;
-  for (int r = 0; r < rows; ++r) {
-    const long long o = (long long)(m0 + r) * C + c;
-    const float xv = Elt<DT>::to_f32(((const T*)x)[o]);
-    float d = 0.f;
-#pragma unroll
-    for (int j = 0; j < JMAX; ++j) {
-      aw[j] += g[r][j] * xv;
-      d += g[r][j] * wr[j];
-    }
-    if (relu && !(xv > 0.f)) d = 0.f;
-    cs += d;
-    ((T*)dz)[o] = Elt<DT>::from_f32(d);
-  }
-#pragma unroll
-  for (int j = 0; j < JMAX; ++j)
-    if (j < J) out[(long long)j * C + c] = aw[j];
-  out[J * C + J + c] = cs;
-}
 
 // ---- fastrcnn_loss ----------------------------------------------------------------------------------------------------
 //   losses[0] = mean_i ( logsumexp(z_i) - z_i[label_i] )
@@ -140,19 +53,11 @@ __global__ __launch_bounds__(1024) void fastrcnn_loss_kernel(const float* __rest
       sb += (double)b;
     }
   }
-  red[0][threadIdx.x] = sc;
-  red[1][threadIdx.x] = sb;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      red[0][threadIdx.x] += red[0][threadIdx.x + o];
-      red[1][threadIdx.x] += red[1][threadIdx.x + o];
-    }
-    __syncthreads();
-  }
+  sc = block_sum_1024(red[0], sc);
+  sb = block_sum_1024(red[1], sb);
   if (threadIdx.x == 0) {
-    losses[0] = (float)(red[0][0] / (double)N);
-    losses[1] = (float)(red[1][0] / (double)N);
+    losses[0] = (float)(sc / (double)N);
+    losses[1] = (float)(sb / (double)N);
   }
 }
 
@@ -399,44 +304,9 @@ __global__ __launch_bounds__(64) void det_scan_kernel(const float* __restrict__ 
   }
 }
 
-static int check_classes(const char* what, int num_classes) {
-  SFVOS_REQUIRE(num_classes >= 1 && num_classes <= BP_MAXK, "%s: num_classes %d out of [1, %d]", what, num_classes,
-                BP_MAXK);
-  return SFVOS_OK;
-}
 }  // namespace sfvos
 
 using namespace sfvos;
-
-extern "C" int sfvos_box_predictor(const void* x, int dtype, const float* w_cls, const float* b_cls, const float* w_box,
-                                   const float* b_box, int m, int c, int num_classes, float* logits, float* deltas,
-                                   sfvos_stream_t stream) {
-  SFVOS_REQUIRE(x && w_cls && w_box && logits && deltas && m > 0 && c > 0, "box_predictor: bad argument");
-  if (int rc = check_classes("box_predictor", num_classes)) return rc;
-  return launch_dt(dtype, "box_predictor", [&](auto dt) {
-    hipLaunchKernelGGL(box_predictor_kernel<dt>, dim3((unsigned)ceil_div(m, 4)), dim3(256), 0, (hipStream_t)stream,
-                       (const char*)x, w_cls, b_cls, w_box, b_box, m, c, num_classes, logits, deltas);
-  });
-}
-
-extern "C" int sfvos_box_predictor_bwd_rows(int m) { return m > 0 ? ceil_div(m, BPB_ROWS) : 0; }
-
-extern "C" int sfvos_box_predictor_bwd(const void* x, int dtype, const float* dlogits, const float* ddeltas,
-                                       const float* w_cls, const float* w_box, int m, int c, int num_classes, int relu,
-                                       void* dz, float* part, sfvos_stream_t stream) {
-  SFVOS_REQUIRE(x && dlogits && ddeltas && w_cls && w_box && dz && part && m > 0 && c > 0,
-                "box_predictor_bwd: bad argument");
-  if (int rc = check_classes("box_predictor_bwd", num_classes)) return rc;
-  dim3 grid((unsigned)ceil_div(m, BPB_ROWS), (unsigned)ceil_div(c, 256));
-  return launch_dt(dtype, "box_predictor_bwd", [&](auto dt) {
-    if (num_classes <= 2)
-      hipLaunchKernelGGL((box_predictor_bwd_kernel<dt, 10>), grid, dim3(256), 0, (hipStream_t)stream, (const char*)x,
-                         dlogits, ddeltas, w_cls, w_box, m, c, num_classes, relu, (char*)dz, part);
-    else
-      hipLaunchKernelGGL((box_predictor_bwd_kernel<dt, 5 * BP_MAXK>), grid, dim3(256), 0, (hipStream_t)stream,
-                         (const char*)x, dlogits, ddeltas, w_cls, w_box, m, c, num_classes, relu, (char*)dz, part);
-  });
-}
 
 extern "C" int sfvos_fastrcnn_loss(const float* logits, const float* deltas, const int64_t* labels, const float* targets,
                                    int n, int num_classes, float beta, float* losses, sfvos_stream_t stream) {

@@ -1,5 +1,6 @@
-// Helpers shared by the HBM-bound kernels (elementwise.hip, batchnorm.hip, maskhead.hip, window_shift.hip): 16-byte
-// pack/unpack, deterministic column sums; on the host, the f32 / bf16 activation checks and dtype dispatch.
+// Helpers shared by the HBM-bound kernels (elementwise.hip, batchnorm.hip, maskhead.hip, window_shift.hip) and the
+// roi_heads files (project.hip, boxes.hip): 16-byte pack/unpack, deterministic column and block sums; on the host, the
+// f32 / bf16 activation checks, the class-count check and dtype dispatch.
 #pragma once
 #include <type_traits>
 
@@ -79,6 +80,18 @@ __device__ __forceinline__ double column_sum(const float* part, int rows, int nc
   return tot;
 }
 
+// Sum of one double per thread of a 1024-thread block in a fixed tree order (512, 256, ..., 1); red: 1024 doubles of
+// LDS of the caller's (one array per sum).  Every thread gets the total.
+__device__ __forceinline__ double block_sum_1024(double* red, double v) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  return red[0];
+}
+
 static inline unsigned grid_for(long long work_items, int per_block, unsigned cap = 2048u * 4u) {
   long long g = ceil_div64(work_items, per_block);
   if (g < 1) g = 1;
@@ -97,6 +110,14 @@ static inline int check_act(const char* what, int dtype, int C, int ld_a, int ld
   SFVOS_REQUIRE(C > 0 && C % 32 == 0 && C <= 256, "%s: C %d must be a multiple of 32, <= 256", what, C);
   SFVOS_REQUIRE(ld_a >= C && ld_b >= C && ld_a % ce == 0 && ld_b % ce == 0,
                 "%s: pitches %d, %d must be >= C and multiples of %d", what, ld_a, ld_b, ce);
+  return SFVOS_OK;
+}
+
+// Classes of the roi_heads entry points that cap them (project.hip, boxes.hip)
+constexpr int HEAD_MAXK = 8;
+static inline int check_classes(const char* what, int num_classes) {
+  SFVOS_REQUIRE(num_classes >= 1 && num_classes <= HEAD_MAXK, "%s: num_classes %d out of [1, %d]", what, num_classes,
+                HEAD_MAXK);
   return SFVOS_OK;
 }
 

@@ -7,7 +7,7 @@
 //   RoI features [N,256,14,14] -> 4 x (conv3x3 256->256 + ReLU)        sfvos_conv3d (kt = 1, relu epilogue)
 //                              -> ConvTranspose2d 2x2 stride 2 + ReLU   sfvos_deconv2x2_relu      (this file)
 //                              -> conv1x1 256 -> num_classes, sigmoid, the box's label channel
-//                                                                       sfvos_mask_logits         (this file)
+//                                                                       sfvos_mask_logits         (project.hip)
 //                              -> masks padded by 1, boxes expanded, bilinear resize to the box, paste into the image
 //                                                                       sfvos_paste_masks         (this file)
 //
@@ -70,39 +70,6 @@ __global__ __launch_bounds__(256) void pack_deconv_kernel(const float* __restric
     const long long col = i / c_in;
     const int ab = (int)(col / c_out), co = (int)(col - (long long)ab * c_out);
     ((T*)wp)[i] = Elt<DT>::from_f32(w[((long long)ci * c_out + co) * 4 + ab]);
-  }
-}
-
-// ---- mask_fcn_logits (conv1x1 C -> num_classes) + sigmoid + label select ---------------------------------------
-// one wave per pixel: 64 lanes x C/64 channels, shuffle reduction.  logits [N][K][P] (optional, all classes),
-// prob [N][1][P] = sigmoid(logit of class labels[n]) (maskrcnn_inference).
-template <int DT>
-__global__ __launch_bounds__(256) void mask_logits_kernel(const char* __restrict__ x, const float* __restrict__ w,
-                                                          const float* __restrict__ bias,
-                                                          const long long* __restrict__ labels, int N, int P, int C,
-                                                          int K, float* logits, float* prob) {
-  typedef typename Elt<DT>::type T;
-  const int lane = threadIdx.x & 63;
-  const long long pix = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (pix >= (long long)N * P) return;
-  const int n = (int)(pix / P), p = (int)(pix - (long long)n * P);
-  const T* xr = (const T*)x + pix * C;
-  // a label outside [0, K) selects no channel: prob becomes NaN (torch raises an index error there; an
-  // out-of-range label must never turn into an out-of-bounds access or an uninitialised result)
-  const long long lab64 = labels ? labels[n] : 0;
-  const int lab = (lab64 >= 0 && lab64 < K) ? (int)lab64 : -1;
-  if (prob && lab < 0 && lane == 0) prob[(long long)n * P + p] = __builtin_nanf("");
-  for (int k = 0; k < K; ++k) {
-    if (!logits && k != lab) continue;
-    float s = 0.f;
-    for (int c = lane; c < C; c += 64) s += Elt<DT>::to_f32(xr[c]) * w[(long long)k * C + c];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    s += bias ? bias[k] : 0.f;
-    if (lane == 0) {
-      if (logits) logits[((long long)n * K + k) * P + p] = s;
-      if (prob && k == lab) prob[(long long)n * P + p] = 1.f / (1.f + expf(-s));
-    }
   }
 }
 
@@ -217,13 +184,8 @@ __global__ __launch_bounds__(1024) void mask_bce_loss_kernel(const float* __rest
     const float z = logits[((long long)n * K + (int)lab) * P + p], t = targets[i];
     s += (double)(fmaxf(z, 0.f) - z * t + log1pf(expf(-fabsf(z))));
   }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss[0] = (float)(red[0] / (double)total);
+  s = block_sum_1024(red, s);
+  if (threadIdx.x == 0) loss[0] = (float)(s / (double)total);
 }
 
 //   dlogits[n][k][p] = k == labels[n] ? upstream * (sigmoid(z) - t) / (N P) : 0
@@ -245,75 +207,6 @@ __global__ __launch_bounds__(256) void mask_bce_grad_kernel(const float* __restr
     }
     dlogits[i] = g;
   }
-}
-
-// ---- backward of mask_fcn_logits (conv1x1 C -> K) and of the ReLU in front of it ----------------------------------
-//   dz[n][p][c] = y[n][p][c] > 0 ? sum_k dl[n][k][p] w[k][c] : 0          (gradient w.r.t. the deconv's pre-ReLU output)
-//   part[block] = [ sum dl[k] y[c]  (K x C) | sum dl[k]  (K) | sum dz[c]  (C) ]   over the block's MLB_PIX pixels
-// wave = 16 pixels, lane = channels lane, lane + 64, ...
-constexpr int MLB_PIX = 64, MLB_MAXK = 8, MLB_MAXQ = 8;
-template <int DT>
-__global__ __launch_bounds__(256) void mask_logits_bwd_kernel(const char* __restrict__ y, const float* __restrict__ dl,
-                                                              const float* __restrict__ w, int N, int P, int C, int K,
-                                                              int relu, char* dz, float* part) {
-  typedef typename Elt<DT>::type T;
-  extern __shared__ float red[];  // [4 waves][K*C + K + C]
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int Q = C / 64, L = K * C + K + C;
-  float aw[MLB_MAXK][MLB_MAXQ], ab[MLB_MAXK], cs[MLB_MAXQ], wr[MLB_MAXK][MLB_MAXQ];
-#pragma unroll
-  for (int k = 0; k < MLB_MAXK; ++k) {
-    ab[k] = 0.f;
-#pragma unroll
-    for (int q = 0; q < MLB_MAXQ; ++q) {
-      aw[k][q] = 0.f;
-      wr[k][q] = (k < K && q < Q) ? w[(long long)k * C + lane + 64 * q] : 0.f;
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < MLB_MAXQ; ++q) cs[q] = 0.f;
-  const long long total = (long long)N * P;
-  const long long pix0 = (long long)blockIdx.x * MLB_PIX + wv * (MLB_PIX / 4);
-  for (int i = 0; i < MLB_PIX / 4; ++i) {
-    const long long pix = pix0 + i;
-    if (pix >= total) break;  // wave-uniform
-    const int n = (int)(pix / P), p = (int)(pix - (long long)n * P);
-    float g[MLB_MAXK];
-#pragma unroll
-    for (int k = 0; k < MLB_MAXK; ++k) g[k] = k < K ? dl[((long long)n * K + k) * P + p] : 0.f;
-#pragma unroll
-    for (int k = 0; k < MLB_MAXK; ++k) ab[k] += g[k];
-#pragma unroll
-    for (int q = 0; q < MLB_MAXQ; ++q) {
-      if (q >= Q) break;
-      const long long o = pix * C + lane + 64 * q;
-      const float yv = Elt<DT>::to_f32(((const T*)y)[o]);
-      float d = 0.f;
-#pragma unroll
-      for (int k = 0; k < MLB_MAXK; ++k) {
-        aw[k][q] += g[k] * yv;
-        d += g[k] * wr[k][q];
-      }
-      if (relu && !(yv > 0.f)) d = 0.f;
-      cs[q] += d;
-      ((T*)dz)[o] = Elt<DT>::from_f32(d);
-    }
-  }
-  float* mine = red + wv * L;
-#pragma unroll
-  for (int k = 0; k < MLB_MAXK; ++k) {
-    if (k >= K) break;
-#pragma unroll
-    for (int q = 0; q < MLB_MAXQ; ++q)
-      if (q < Q) mine[k * C + lane + 64 * q] = aw[k][q];
-    if (lane == 0) mine[K * C + k] = ab[k];
-  }
-#pragma unroll
-  for (int q = 0; q < MLB_MAXQ; ++q)
-    if (q < Q) mine[K * C + K + lane + 64 * q] = cs[q];
-  __syncthreads();
-  for (int i = threadIdx.x; i < L; i += 256)
-    part[(long long)blockIdx.x * L + i] = (red[i] + red[L + i]) + (red[2 * L + i] + red[3 * L + i]);
 }
 
 // ---- ConvTranspose2d(2, 2, 0) backward ------------------------------------------------------------------------------
@@ -444,19 +337,6 @@ extern "C" int sfvos_deconv2x2_relu(const void* x, const void* w_packed, const f
   }, "deconv2x2");
 }
 
-extern "C" int sfvos_mask_logits(const void* x, int dtype, const float* w, const float* bias, const int64_t* labels,
-                                 int n, int positions, int c, int num_classes, float* logits, float* prob,
-                                 sfvos_stream_t stream) {
-  SFVOS_REQUIRE(x && w && n > 0 && positions > 0 && c > 0 && num_classes > 0 && (logits || prob),
-                "mask_logits: bad argument");
-  SFVOS_REQUIRE(!prob || labels || num_classes == 1, "mask_logits: prob needs the labels of the boxes");
-  const long long pix = (long long)n * positions;
-  return launch_dt(dtype, "mask_logits", [&](auto dt) {
-    hipLaunchKernelGGL(mask_logits_kernel<dt>, dim3((unsigned)ceil_div64(pix, 4)), dim3(256), 0, (hipStream_t)stream,
-                       (const char*)x, w, bias, (const long long*)labels, n, positions, c, num_classes, logits, prob);
-  });
-}
-
 extern "C" int sfvos_paste_masks(const float* masks, const float* boxes, int n, int mask_size, int padding, int img_h,
                                  int img_w, float* out, sfvos_stream_t stream) {
   SFVOS_REQUIRE(masks && boxes && out && n > 0 && mask_size > 0 && padding >= 0 && img_h > 0 && img_w > 0,
@@ -499,31 +379,6 @@ extern "C" int sfvos_mask_bce_loss_grad(const float* logits, const int64_t* labe
                      (hipStream_t)stream, logits, (const long long*)labels, targets, upstream, n, num_classes, positions,
                      dlogits);
   return check_launch("mask_bce_loss_grad");
-}
-
-extern "C" int sfvos_mask_logits_bwd_rows(int n, int positions) {
-  return n > 0 && positions > 0 ? (int)ceil_div64((long long)n * positions, MLB_PIX) : 0;
-}
-
-extern "C" int sfvos_mask_logits_bwd(const void* y, int dtype, const float* dlogits, const float* w, int n, int positions,
-                                     int c, int num_classes, int relu, void* dz, float* part, sfvos_stream_t stream) {
-  SFVOS_REQUIRE(y && dlogits && w && dz && part && n > 0 && positions > 0, "mask_logits_bwd: bad argument");
-  SFVOS_REQUIRE(c > 0 && c % 64 == 0 && c / 64 <= MLB_MAXQ && num_classes > 0 && num_classes <= MLB_MAXK,
-                "mask_logits_bwd: C must be a multiple of 64 (<= %d), num_classes <= %d", 64 * MLB_MAXQ, MLB_MAXK);
-  const unsigned grid = (unsigned)ceil_div64((long long)n * positions, MLB_PIX);
-  const int lds = 4 * (num_classes * c + num_classes + c) * (int)sizeof(float);
-  // c = 512 with 7 or 8 classes needs 65 648 / 73 856 bytes, above the 64 KB a kernel gets by default: the limit is
-  // raised once per (kernel instance, device) to what the largest admitted shape needs
-  constexpr int lds_max = 4 * (MLB_MAXK * 64 * MLB_MAXQ + MLB_MAXK + 64 * MLB_MAXQ) * (int)sizeof(float);
-  int attr_rc = SFVOS_OK;
-  const int rc = launch_dt(dtype, "mask_logits_bwd", [&](auto dt) {
-    static LdsAttrOnce once;
-    attr_rc = once.ensure((const void*)mask_logits_bwd_kernel<dt>, lds_max, "mask_logits_bwd");
-    if (attr_rc) return;
-    hipLaunchKernelGGL(mask_logits_bwd_kernel<dt>, dim3(grid), dim3(256), lds, (hipStream_t)stream, (const char*)y,
-                       dlogits, w, n, positions, c, num_classes, relu, (char*)dz, part);
-  });
-  return attr_rc ? attr_rc : rc;
 }
 
 extern "C" int sfvos_pack_deconv2x2_dgrad(const float* w, void* packed, int dtype, int c_in, int c_out,

@@ -22,39 +22,8 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._heads import _check_gpu, _check_precision, _f32, _pack, _project_bwd, _reduce_rows, _to_nchw, _to_nhwc
 from .module import _DT, _conv_desc, _ptr, _stream
-
-
-def _check_gpu(t, what):
-    if not t.is_cuda:
-        raise RuntimeError('%s runs on the GPU through libsfvos.so (no CPU fallback)' % what)
-    _lib.load()
-
-
-def _to_nhwc(x, dt_id, tdt):
-    """[N,C,H,W] fp32 (any strides) -> NHWC [N,H,W,C] in the compute dtype (sfvos_frames_to_ndhwc with T = N)."""
-    N, C, H, W = x.shape
-    s = x if x.dtype == torch.float32 else x.float()
-    out = torch.empty((N, H, W, C), dtype=tdt, device=x.device)
-    _lib.call('sfvos_frames_to_ndhwc', _ptr(s), s.stride(0), s.stride(1), s.stride(2), s.stride(3), _ptr(out), dt_id,
-              N, C, H, W, C, _stream())
-    return out
-
-
-def _pack(fn, w, dt_id, tdt, *shape):
-    """Packed image of weight w (fp32 copy) by the libsfvos packer fn (shape: its size arguments)."""
-    wc = w.detach().float().contiguous()
-    packed = torch.empty(wc.numel(), dtype=tdt, device=w.device)
-    _lib.call(fn, _ptr(wc), _ptr(packed), dt_id, *(shape + (_stream(),)))
-    return packed
-
-
-def _to_nchw(x_nhwc, dt_id):
-    N, H, W, C = x_nhwc.shape
-    out = torch.empty((N, C, H, W), dtype=torch.float32, device=x_nhwc.device)
-    _lib.call('sfvos_ndhwc_to_frames', _ptr(x_nhwc), dt_id, _ptr(out), out.stride(0), out.stride(1), out.stride(2),
-              out.stride(3), N, C, H, W, C, 0, _stream())
-    return out
 
 
 class MaskRCNNHeads(nn.Module):
@@ -65,9 +34,7 @@ class MaskRCNNHeads(nn.Module):
         super(MaskRCNNHeads, self).__init__()
         if dilation != 1:
             raise ValueError('MaskRCNNHeads: only dilation 1 (the reference configuration) is implemented')
-        if precision not in ('fp32', 'bf16'):
-            raise ValueError("precision must be 'fp32' or 'bf16'")
-        self.precision = precision
+        self.precision = _check_precision(precision)
         self.n_layers = len(layers)
         nf = in_channels
         for i, feat in enumerate(layers, 1):
@@ -113,9 +80,7 @@ class MaskRCNNPredictor(nn.Module):
 
     def __init__(self, in_channels=256, dim_reduced=256, num_classes=2, precision='fp32'):
         super(MaskRCNNPredictor, self).__init__()
-        if precision not in ('fp32', 'bf16'):
-            raise ValueError("precision must be 'fp32' or 'bf16'")
-        self.precision = precision
+        self.precision = _check_precision(precision)
         self.conv5_mask = nn.ConvTranspose2d(in_channels, dim_reduced, 2, 2, 0)
         self.relu = nn.ReLU(inplace=True)
         self.mask_fcn_logits = nn.Conv2d(dim_reduced, num_classes, 1, 1, 0)
@@ -145,7 +110,7 @@ class MaskRCNNPredictor(nn.Module):
         N, H, W, C = y_nhwc.shape
         conv = self.mask_fcn_logits
         K = conv.out_channels
-        wl = conv.weight.detach().float().reshape(K, C).contiguous()
+        wl = _f32(conv.weight).reshape(K, C)
         logits = torch.empty((N, K, H, W), dtype=torch.float32, device=y_nhwc.device) if want_logits else None
         prob = torch.empty((N, 1, H, W), dtype=torch.float32, device=y_nhwc.device) if want_prob else None
         lab = None
@@ -172,7 +137,7 @@ def maskrcnn_inference(mask_logits, labels):
     [N,1,M,M].  (When the heads above produced the logits, MaskBranch.predict fuses this into the logits kernel.)"""
     _check_gpu(mask_logits, 'maskrcnn_inference')
     N, K, H, W = mask_logits.shape
-    x = mask_logits.detach().float().permute(0, 2, 3, 1).contiguous()        # NHWC view of the K logits
+    x = _f32(mask_logits.permute(0, 2, 3, 1))                                # NHWC copy of the K logits
     eye = torch.eye(K, dtype=torch.float32, device=x.device)
     prob = torch.empty((N, 1, H, W), dtype=torch.float32, device=x.device)
     lab = labels.to(device=x.device, dtype=torch.int64).contiguous()
@@ -188,8 +153,8 @@ def paste_masks_in_image(masks, boxes, img_shape, padding=1):
     if masks.shape[0] == 0:
         return masks.new_empty((0, 1, im_h, im_w))
     _check_gpu(masks, 'paste_masks_in_image')
-    m = masks.detach().float().contiguous()
-    b = boxes.detach().to(device=m.device, dtype=torch.float32).contiguous()
+    m = _f32(masks)
+    b = _f32(boxes, m.device)
     out = torch.empty((m.shape[0], 1, im_h, im_w), dtype=torch.float32, device=m.device)
     _lib.call('sfvos_paste_masks', _ptr(m), _ptr(b), m.shape[0], m.shape[-1], int(padding), im_h, im_w, _ptr(out),
               _stream())
@@ -229,17 +194,10 @@ class _MaskBranchFn(torch.autograd.Function):
         conv = pred.mask_fcn_logits
         K, C = conv.out_channels, conv.in_channels
         P2 = 4 * H * W
-        dl = dlogits.detach().float().contiguous()
-        rows = _lib.load().sfvos_mask_logits_bwd_rows(N, P2)
-        L = K * C + K + C
-        part = torch.empty((rows, L), **f32)
-        dz = torch.empty_like(y5)
-        wl = conv.weight.detach().float().reshape(K, C).contiguous()
-        _lib.call('sfvos_mask_logits_bwd', _ptr(y5), dt_id, _ptr(dl), _ptr(wl), N, P2, C, K, 1, _ptr(dz), _ptr(part),
-                  _stream())
-        comb = torch.empty(L, **f32)
-        _lib.call('sfvos_reduce_rows', _ptr(part), rows, L, _ptr(comb), 0, _stream())
-        g_wl, g_bl, g_b5 = comb[:K * C].view(K, C, 1, 1), comb[K * C:K * C + K], comb[K * C + K:]
+        dz, g_wl, g_bl, g_b5 = _project_bwd('sfvos_mask_logits_bwd', y5, dt_id,
+                                            (_f32(dlogits), _f32(conv.weight).reshape(K, C)), (N, P2, C, K),
+                                            _lib.load().sfvos_mask_logits_bwd_rows(N, P2), K)
+        g_wl = g_wl.view(K, C, 1, 1)
         # ---- conv5_mask (ConvTranspose2d 2x2 s2)
         w5 = pred.conv5_mask.weight
         ci5, co5 = w5.shape[0], w5.shape[1]
@@ -262,8 +220,7 @@ class _MaskBranchFn(torch.autograd.Function):
             rrows = lib.sfvos_relu_bwd_rows(M)
             rpart = torch.empty((rrows, cout), **f32)
             _lib.call('sfvos_relu_bwd', _ptr(cur), _ptr(acts[i]), _ptr(cur), dt_id, M, cout, _ptr(rpart), _stream())
-            g_b = torch.empty(cout, **f32)
-            _lib.call('sfvos_reduce_rows', _ptr(rpart), rrows, cout, _ptr(g_b), 0, _stream())
+            g_b = _reduce_rows(rpart)
             d = _conv3x3_desc(dt_id, N, H, W, cin, cout)
             g_w = torch.empty(conv.weight.shape, **f32)
             wsz = lib.sfvos_conv3d_wgrad_workspace_bytes(ctypes.byref(d))
@@ -289,9 +246,9 @@ class _MaskLossFn(torch.autograd.Function):
     def forward(ctx, logits, labels, targets):
         N, K = logits.shape[0], logits.shape[1]
         P = logits[0, 0].numel()
-        lg = logits.detach().float().contiguous()
+        lg = _f32(logits)
         lab = labels.to(device=lg.device, dtype=torch.int64).contiguous()
-        tg = targets.detach().to(device=lg.device, dtype=torch.float32).contiguous()
+        tg = _f32(targets, lg.device)
         if lab.numel() != N or tg.numel() != N * P:
             raise RuntimeError('maskrcnn_loss: one label and one [M,M] target per RoI expected')
         loss = torch.empty((), dtype=torch.float32, device=lg.device)
@@ -304,7 +261,7 @@ class _MaskLossFn(torch.autograd.Function):
         lg, lab, tg = ctx.saved_tensors
         N, K = lg.shape[0], lg.shape[1]
         P = lg[0, 0].numel()
-        upc = up.detach().float().contiguous()
+        upc = _f32(up)
         d = torch.empty_like(lg)
         _lib.call('sfvos_mask_bce_loss_grad', _ptr(lg), _ptr(lab), _ptr(tg), _ptr(upc), N, K, P, _ptr(d), _stream())
         return d, None, None

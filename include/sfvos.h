@@ -436,9 +436,7 @@ int sfvos_mask_bce_loss_grad(const float* logits, const int64_t* labels, const f
  * dz[n][p][c] = (relu == 0 || y > 0) ? sum_k dlogits[n][k][p] w[k][c] : 0   (dtype, same shape as y);
  * part: sfvos_mask_logits_bwd_rows(n, positions) rows of [num_classes*c + num_classes + c] fp32 =
  * (grad of w | grad of the logits bias | column sums of dz = grad of the deconv bias) partials (sfvos_reduce_rows).
- * c: a multiple of 64 up to 512; num_classes <= 8.  The kernel uses 16 * (num_classes * c + num_classes + c) bytes of
- * dynamic LDS, up to 73 856 at c = 512, num_classes = 8: the entry point raises the kernel's dynamic-LDS limit above
- * the default 64 KB itself (once per device). */
+ * Each partial row covers 64 consecutive rows (n, p) of y.  c: a multiple of 64 up to 512; num_classes <= 8. */
 int sfvos_mask_logits_bwd_rows(int n, int positions);
 int sfvos_mask_logits_bwd(const void* y, int dtype, const float* dlogits, const float* w, int n, int positions, int c,
                           int num_classes, int relu, void* dz, float* part, sfvos_stream_t stream);

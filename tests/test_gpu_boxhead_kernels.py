@@ -1,5 +1,5 @@
-"""GPU: the box-branch kernels (csrc/dense.hip, csrc/boxes.hip) one by one through the C ABI, each against float64 on the
-operands the kernel sees, under the per-element criterion of tests/test_gpu_maskhead_kernels.py (see its docstring):
+"""GPU: the box-branch kernels (csrc/dense.hip, csrc/boxes.hip, csrc/project.hip) one by one through the C ABI, each
+against float64 on the operands the kernel sees, under the per-element criterion of tests/test_gpu_maskhead_kernels.py (see its docstring):
 
     |got - ref|  <=  u_out * |ref|  +  2 * (K + 1) * 2^-22 * mag
 
@@ -270,6 +270,40 @@ def test_box_predictor_bwd(lib, prec, relu, m, c, K):
     check(tag + 'grad w', r[:J * c].view(J, c), gcat.t() @ x.double(), gcat.abs().t() @ x.double().abs(), Kp, 0.0)
     check(tag + 'grad b', r[J * c:J * c + J], gcat.sum(0), gcat.abs().sum(0), Kp, 0.0)
     check(tag + 'column sums of dz', r[J * c + J:], dz_ref.sum(0), dz_mag.sum(0), Kp, 0.0)
+
+
+@pytest.mark.parametrize('prec', PRECS)
+@pytest.mark.parametrize('m,c', [(1, 64), (130, 128)])
+def test_box_and_mask_projections_are_one_kernel(lib, prec, m, c):
+    """The box predictor with one class (J = 5 outputs) and the mask head's entry points called with positions = 1,
+    num_classes = 5 on the concatenated weights are the same projection: outputs, dz and the raw partial rows are equal
+    bit for bit, forward and backward (ReLU on and off)."""
+    K, J = 1, 5
+    x, wc, bc, wb, bb = predictor_operands(m, c, K, prec, 54)
+    g = torch.Generator().manual_seed(55)
+    dl, dd = torch.randn(m, K, generator=g), torch.randn(m, 4 * K, generator=g)
+    xd, wcd, bcd, wbd, bbd = x.to(TDT[prec]).cuda(), wc.cuda(), bc.cuda(), wb.cuda(), bb.cuda()
+    wcat, bcat = torch.cat([wc, wb], 0).cuda(), torch.cat([bc, bb], 0).cuda()
+    dld, ddd, gcat = dl.cuda(), dd.cuda(), torch.cat([dl, dd], 1).cuda()
+    lo, de, both = Out((m, K)), Out((m, 4 * K)), Out((m, J))
+    lib.call('sfvos_box_predictor', P(xd), DT(lib, prec), P(wcd), P(bcd), P(wbd), P(bbd), m, c, K, P(lo.t), P(de.t), S())
+    lib.call('sfvos_mask_logits', P(xd), DT(lib, prec), P(wcat), P(bcat), None, m, 1, c, J, P(both.t), None, S())
+    torch.cuda.synchronize()
+    assert torch.equal(torch.cat([lo.cpu(), de.cpu()], 1), both.cpu())
+    rows = lib.load().sfvos_box_predictor_bwd_rows(m)
+    assert rows == lib.load().sfvos_mask_logits_bwd_rows(m, 1)
+    L = J * c + J + c
+    for relu in (1, 0):
+        dz_b, part_b = Out((m, c), TDT[prec]), Out((rows, L), fill=float('nan'))
+        dz_m, part_m = Out((m, c), TDT[prec]), Out((rows, L), fill=float('nan'))
+        lib.call('sfvos_box_predictor_bwd', P(xd), DT(lib, prec), P(dld), P(ddd), P(wcd), P(wbd), m, c, K, relu,
+                 P(dz_b.t), P(part_b.t), S())
+        lib.call('sfvos_mask_logits_bwd', P(xd), DT(lib, prec), P(gcat), P(wcat), m, 1, c, J, relu, P(dz_m.t),
+                 P(part_m.t), S())
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(part_b.cpu()).all()) and bool(torch.isfinite(part_m.cpu()).all())
+        assert torch.equal(dz_b.cpu(), dz_m.cpu()), 'dz differs (relu %d)' % relu
+        assert torch.equal(part_b.cpu(), part_m.cpu()), 'partial rows differ (relu %d)' % relu
 
 
 # ---- fastrcnn_loss ------------------------------------------------------------------------------------------------------

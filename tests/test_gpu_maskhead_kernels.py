@@ -382,14 +382,14 @@ def test_mask_logits_sigmoid_saturates(lib, prec):
 @pytest.mark.parametrize('relu', [1, 0])
 @pytest.mark.parametrize('case', [
     (9, 784, 256, 2),    # the module's
-    (1, 3, 64, 1),       # less than one wave's 16 pixels
-    (2, 41, 128, 5),     # 82 pixels: the second block has two idle waves
-    (3, 196, 512, 6),    # 57 440 bytes of LDS: the largest below 64 KB
-    (2, 100, 512, 8),    # 73 856 bytes: needs the raised dynamic-LDS limit
+    (1, 3, 64, 1),       # 3 of a block's 64 pixels; a quarter of its 256 column threads
+    (2, 41, 128, 5),     # 82 pixels: the first block spans both RoIs, the second has 18
+    (3, 196, 512, 6),    # the largest C: two column blocks
+    (2, 100, 512, 8),    # the largest C with the most classes
 ])
 def test_mask_logits_bwd(lib, prec, case, relu):
     """dz: K = num_classes.  The three partial blocks (weight gradient | logits-bias gradient | column sums of dz) after
-    sfvos_reduce_rows: K = 64 + rows (a block sums its 64 pixels in fp32: 16 per wave, then the four waves;
+    sfvos_reduce_rows: K = 64 + rows (a block sums its 64 pixels in fp32, one after the other;
     sfvos_reduce_rows adds the rows in f64).  The column sums are those of the unrounded dz.  y holds exact zeros, -0.0
     and a few negative values; part is exactly sfvos_mask_logits_bwd_rows rows, NaN-filled."""
     n, pos, C, K = case
