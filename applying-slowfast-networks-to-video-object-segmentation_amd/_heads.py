@@ -1,29 +1,16 @@
-"""What the two branches of roi_heads (mask_head.py, box_head.py) share on the host: argument checks, fp32 operand
-copies, layout changes, the packer call, and the backward of the class projection both branches end with."""
+"""What the two branches of roi_heads (mask_head.py, box_head.py) share on the host: the precision check, layout
+changes, the packer call, and the two backward steps both branches take: ReLU backward with its bias gradient, and the
+backward of the class projection they end with."""
 import torch
 
 from . import _lib
-from .module import _ptr, _stream
-
-
-def _check_gpu(t, what):
-    if not t.is_cuda:
-        raise RuntimeError('%s runs on the GPU through libsfvos.so (no CPU fallback)' % what)
-    _lib.load()
+from ._lib import _f32, _ptr, _stream
 
 
 def _check_precision(precision):
     if precision not in ('fp32', 'bf16'):
         raise ValueError("precision must be 'fp32' or 'bf16'")
     return precision
-
-
-def _f32(t, dev=None):
-    """t as a detached, contiguous fp32 tensor (on dev), without a copy where it already is one."""
-    t = t.detach()
-    if dev is not None and t.device != dev:
-        t = t.to(dev)
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
 
 
 def _to_nhwc(x, dt_id, tdt):
@@ -57,6 +44,16 @@ def _reduce_rows(part):
     out = torch.empty(part.shape[1], dtype=torch.float32, device=part.device)
     _lib.call('sfvos_reduce_rows', _ptr(part), part.shape[0], part.shape[1], _ptr(out), 0, _stream())
     return out
+
+
+def _relu_bwd(dy, a, dt_id):
+    """ReLU backward in place, dy [..., C] = a > 0 ? dy : 0, and the gradient [C] of the bias of the layer that produced
+    a: the column sums of the new dy, from the partial rows sfvos_relu_bwd leaves."""
+    C = dy.shape[-1]
+    M = dy.numel() // C
+    part = torch.empty((_lib.load().sfvos_relu_bwd_rows(M), C), dtype=torch.float32, device=dy.device)
+    _lib.call('sfvos_relu_bwd', _ptr(dy), _ptr(a), _ptr(dy), dt_id, M, C, _ptr(part), _stream())
+    return _reduce_rows(part)
 
 
 def _project_bwd(fn, x, dt_id, operands, dims, rows, J):

@@ -5,11 +5,13 @@ There is no fallback: if the library is missing or a call fails, a RuntimeError 
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SFVOS_LIB') or os.path.join(_HERE, 'csrc', 'libsfvos.so')  # SFVOS_LIB: A/B builds
 
 F32, BF16, FP8 = 0, 1, 2
-ABI_REVISION = 302   # the revision of include/sfvos.h this binding mirrors
+ABI_REVISION = 303   # the revision of include/sfvos.h this binding mirrors
 MAX_LEVELS = 8
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -83,6 +85,53 @@ def make_levels(shapes, batch, frames):
     return lv
 
 
+# precision -> (dtype id of the entry points, torch dtype of the compute tensors)
+_DT = {'fp32': (F32, torch.float32), 'bf16': (BF16, torch.bfloat16),
+       # 'fp8': inference only; the four Cin = 256 convs (fast_conv1, slow_conv1-3: 99 % of the forward FLOPs) run on
+       # e4m3 operands, the 32-channel layers and every conv RESULT stay bf16
+       'fp8': (BF16, torch.bfloat16)}
+
+
+def _ptr(t, elem_offset=0):
+    """Address of element elem_offset of tensor t; None (a NULL argument) for t = None."""
+    return None if t is None else C.c_void_p(t.data_ptr() + elem_offset * t.element_size())
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _conv_desc(dt_id, batch, pyr, kt, taps, c_in, c_out, t_in, x, ld_y, t_alloc=None, t_offset=0, pad_t=0,
+               accumulate=0, relu=0):
+    """sfvos_conv_desc.  x: pitch of the input in elements, or the input tensor itself ([M, ld] ndhwc, or
+    channel-group-major [C/32][M][32] bf16 / [C/64][M][64] e4m3); t_alloc defaults to t_in."""
+    d = ConvDesc()
+    if torch.is_tensor(x):
+        if x.dim() == 3:
+            d.x_group_stride, x = x.shape[1] * x.shape[2], x.shape[2]
+        else:
+            x = x.shape[-1]
+    d.dtype, d.batch, d.kt, d.taps, d.pyr = dt_id, batch, kt, taps, pyr
+    d.t_in, d.c_in, d.c_out, d.pad_t = t_in, c_in, c_out, pad_t
+    d.t_alloc, d.t_offset = (t_in if t_alloc is None else t_alloc), t_offset
+    d.ld_x, d.ld_y, d.accumulate, d.relu = x, ld_y, accumulate, relu
+    return d
+
+
+def _check_gpu(t, what):
+    if not t.is_cuda:
+        raise RuntimeError('%s runs on the GPU through libsfvos.so (no CPU fallback)' % what)
+    load()
+
+
+def _f32(t, dev=None):
+    """t as a detached, contiguous fp32 tensor (on dev), without a copy where it already is one."""
+    t = t.detach()
+    if dev is not None and t.device != dev:
+        t = t.to(dev)
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
 PD, PL, PM, PR = C.POINTER(ConvDesc), C.POINTER(Levels), C.POINTER(MseTable), C.POINTER(BnRunning)
 
 # name -> (restype, argtypes); every symbol include/sfvos.h declares
@@ -152,8 +201,6 @@ SIGNATURES = {
     'sfvos_dense_workspace_bytes': (C.c_size_t, [i32, i32, i32, i32]),
     'sfvos_dense': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
     'sfvos_dense_wgrad': (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp]),
-    'sfvos_relu_bwd_wide_rows': (i32, [i32]),
-    'sfvos_relu_bwd_wide': (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
     'sfvos_box_predictor': (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     'sfvos_box_predictor_bwd_rows': (i32, [i32]),
     'sfvos_box_predictor_bwd': (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),

@@ -20,9 +20,9 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._heads import _check_gpu, _check_precision, _f32, _pack, _project_bwd, _reduce_rows, _to_nchw, _to_nhwc
+from ._heads import _check_precision, _pack, _project_bwd, _relu_bwd, _to_nchw, _to_nhwc
+from ._lib import _DT, _check_gpu, _f32, _ptr, _stream
 from .mask_head import MaskBranch
-from .module import _DT, _ptr, _stream
 from .roi_align import MultiScaleRoIAlign
 
 BOX_WEIGHTS = (10.0, 10.0, 5.0, 5.0)          # roi_heads' BoxCoder
@@ -43,8 +43,7 @@ def _dense(x, image, bias, dt_id, tdt, n, relu):
     y = torch.empty((M, n), dtype=tdt, device=x.device)
     nbytes = _lib.load().sfvos_dense_workspace_bytes(dt_id, M, n, K)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-    _lib.call('sfvos_dense', _ptr(x), _ptr(image), _ptr(bias) if bias is not None else None, _ptr(y), dt_id, M, n, K,
-              int(relu), _ptr(ws) if ws is not None else None, _stream())
+    _lib.call('sfvos_dense', _ptr(x), _ptr(image), _ptr(bias), _ptr(y), dt_id, M, n, K, int(relu), _ptr(ws), _stream())
     return y
 
 
@@ -159,10 +158,7 @@ class _BoxBranchFn(torch.autograd.Function):
             g_w7 = torch.empty((R, R6), **f32)
             _lib.call('sfvos_dense_wgrad', _ptr(h6), _ptr(dz7), dt_id, N, R, R6, 1, _ptr(g_w7), 0, _stream())
         dz6 = _dense(dz7, head._packed(head.fc7, dt_id, tdt, 1, dgrad=True), None, dt_id, tdt, R6, False)
-        rrow = lib.sfvos_relu_bwd_wide_rows(N)
-        rpart = torch.empty((rrow, R6), **f32)
-        _lib.call('sfvos_relu_bwd_wide', _ptr(dz6), _ptr(h6), _ptr(dz6), dt_id, N, R6, _ptr(rpart), _stream())
-        g_b6 = _reduce_rows(rpart)
+        g_b6 = _relu_bwd(dz6, h6, dt_id)
         # ---- fc6
         Kin = head.fc6.in_features
         g_w6 = None

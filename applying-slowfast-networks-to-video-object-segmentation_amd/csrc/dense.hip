@@ -236,27 +236,6 @@ __global__ __launch_bounds__(256) void dense_wgrad_kernel(const char* __restrict
   }
 }
 
-// ---- ReLU backward of a wide layer + column sums (bias gradient): the [M][C] form of relu_bwd_kernel for any C ----
-//   dz[m][c] = a[m][c] > 0 ? dy[m][c] : 0;  part[row block][c] = sum over the block's DRB_ROWS rows of dz, top down
-constexpr int DRB_ROWS = 64;
-template <int DT>
-__global__ __launch_bounds__(256) void relu_bwd_wide_kernel(const char* dy, const char* __restrict__ a, char* dz, int M,
-                                                            int C, float* part) {
-  typedef typename Elt<DT>::type T;
-  const int c = blockIdx.y * 256 + threadIdx.x;
-  if (c >= C) return;
-  const int m0 = blockIdx.x * DRB_ROWS, m1 = min(M, m0 + DRB_ROWS);
-  float s = 0.f;
-  for (int m = m0; m < m1; ++m) {
-    const long long o = (long long)m * C + c;
-    float g = Elt<DT>::to_f32(((const T*)dy)[o]);
-    if (a && !(Elt<DT>::to_f32(((const T*)a)[o]) > 0.f)) g = 0.f;
-    s += g;
-    if (dz) ((T*)dz)[o] = Elt<DT>::from_f32(g);
-  }
-  if (part) part[(long long)blockIdx.x * C + c] = s;
-}
-
 static int dense_check(const char* what, int dtype, int m, int n, int k) {
   SFVOS_REQUIRE(dtype == SFVOS_F32 || dtype == SFVOS_BF16, "%s: bad dtype %d", what, dtype);
   SFVOS_REQUIRE(m >= 1 && m <= (1 << 20), "%s: rows %d out of [1, 2^20]", what, m);
@@ -349,18 +328,5 @@ extern "C" int sfvos_dense_wgrad(const void* x, const void* dz, int dtype, int m
   return launch_dt(dtype, "dense_wgrad", [&](auto dt) {
     hipLaunchKernelGGL(dense_wgrad_kernel<dt>, dim3((unsigned)ceil_div(tiles, 4)), dim3(256), 0, (hipStream_t)stream,
                        (const char*)x, (const char*)dz, grad_w, m, n, k, positions, accumulate);
-  });
-}
-
-extern "C" int sfvos_relu_bwd_wide_rows(int m) { return m > 0 ? ceil_div(m, DRB_ROWS) : 0; }
-
-extern "C" int sfvos_relu_bwd_wide(const void* dy, const void* a, void* dz, int dtype, int m, int c, float* col_part,
-                                   sfvos_stream_t stream) {
-  SFVOS_REQUIRE(dy && (dz || col_part) && m >= 1 && m <= (1 << 20) && c >= 1 && c <= (1 << 20),
-                "relu_bwd_wide: bad argument");
-  dim3 grid((unsigned)ceil_div(m, DRB_ROWS), (unsigned)ceil_div(c, 256));
-  return launch_dt(dtype, "relu_bwd_wide", [&](auto dt) {
-    hipLaunchKernelGGL(relu_bwd_wide_kernel<dt>, grid, dim3(256), 0, (hipStream_t)stream, (const char*)dy,
-                       (const char*)a, (char*)dz, m, c, col_part);
   });
 }

@@ -125,49 +125,6 @@ __global__ __launch_bounds__(256) void paste_masks_kernel(const float* __restric
 // and the autograd of the modules above.  The 3x3 convs use sfvos_conv3d (data gradient, dgrad-packed weights) and
 // sfvos_conv3d_wgrad; the rest is here.  Everything is reduced in a fixed order (deterministic, no atomics).
 
-// ---- ReLU backward + column sums (bias gradient of the conv that produced `a`) -----------------------------------
-//   dz[m][c] = a[m][c] > 0 ? dy[m][c] : 0 (a == NULL: dz = dy);  part[block][c] = sum over the block's rows of dz
-constexpr int RB_ROWS = 64;  // rows per block
-template <int DT>
-// (dy is not __restrict__: the mask branch calls this in place, dz == dy; every element is read before it is written
-// by the same thread)
-__global__ __launch_bounds__(256) void relu_bwd_kernel(const char* dy, const char* __restrict__ a, char* dz,
-                                                       long long M, int C, float* part) {
-  constexpr int CE = Elt<DT>::CE, ES = 16 / CE;
-  __shared__ float red[256][8];
-  const int cpr = C / CE;              // 16-byte chunks per row (<= 64)
-  const int rl = 256 / cpr;            // row lanes
-  const int ch = threadIdx.x % cpr, rowl = threadIdx.x / cpr;
-  const long long m0 = (long long)blockIdx.x * RB_ROWS;
-  float acc[CE];
-#pragma unroll
-  for (int e = 0; e < CE; ++e) acc[e] = 0.f;
-  if (rowl < rl)
-    for (int i = rowl; i < RB_ROWS && m0 + i < M; i += rl) {
-      const long long o = ((m0 + i) * C + ch * CE) * ES;
-      float g[CE], v[CE];
-      unpack<DT>(*(const u32x4*)(dy + o), g);
-      if (a) {
-        unpack<DT>(*(const u32x4*)(a + o), v);
-#pragma unroll
-        for (int e = 0; e < CE; ++e) g[e] = v[e] > 0.f ? g[e] : 0.f;
-      }
-#pragma unroll
-      for (int e = 0; e < CE; ++e) acc[e] += g[e];
-      if (dz) *(u32x4*)(dz + o) = pack<DT>(g);
-    }
-  if (part == nullptr) return;
-#pragma unroll
-  for (int e = 0; e < CE; ++e) red[threadIdx.x][e] = acc[e];
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += 256) {
-    const int chunk = c / CE, e = c - chunk * CE;
-    float t = 0.f;
-    for (int k = 0; k < rl; ++k) t += red[k * cpr + chunk][e];
-    part[(long long)blockIdx.x * C + c] = t;
-  }
-}
-
 // ---- maskrcnn_loss: BCE with logits on the label's channel, mean over N x P ---------------------------------------
 //   loss = mean( max(z, 0) - z t + log(1 + exp(-|z|)) ),  z = logits[n][labels[n]][p], t = targets[n][p]
 __global__ __launch_bounds__(1024) void mask_bce_loss_kernel(const float* __restrict__ logits,
@@ -344,21 +301,6 @@ extern "C" int sfvos_paste_masks(const float* masks, const float* boxes, int n, 
   hipLaunchKernelGGL(paste_masks_kernel, dim3(grid_for((long long)n * img_h * img_w, 256 * 4)), dim3(256), 0,
                      (hipStream_t)stream, masks, boxes, n, mask_size, padding, img_h, img_w, out);
   return check_launch("paste_masks");
-}
-
-extern "C" int sfvos_relu_bwd_rows(int64_t m) { return m > 0 ? (int)ceil_div64(m, RB_ROWS) : 0; }
-
-extern "C" int sfvos_relu_bwd(const void* dy, const void* a, void* dz, int dtype, int64_t m, int c, float* col_part,
-                              sfvos_stream_t stream) {
-  SFVOS_REQUIRE(dy && m > 0 && (dz || col_part), "relu_bwd: bad argument");
-  const int ce = 16 / elt_bytes(dtype);
-  SFVOS_REQUIRE(c > 0 && c % ce == 0 && c / ce <= 64 && 256 % (c / ce) == 0,
-                "relu_bwd: C must be a power-of-two number (<= 64) of 16-byte chunks");
-  const unsigned grid = (unsigned)ceil_div64(m, RB_ROWS);
-  return launch_dt(dtype, "relu_bwd", [&](auto dt) {
-    hipLaunchKernelGGL(relu_bwd_kernel<dt>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const char*)dy,
-                       (const char*)a, (char*)dz, (long long)m, c, col_part);
-  });
 }
 
 extern "C" int sfvos_mask_bce_loss(const float* logits, const int64_t* labels, const float* targets, int n,

@@ -10,7 +10,7 @@ import ctypes
 import torch
 
 from . import _lib
-from .module import _ptr, _stream
+from ._lib import _check_gpu, _ptr, _stream
 
 
 def _table(outs, targets, grads=None):
@@ -28,8 +28,7 @@ class _MseFn(torch.autograd.Function):
         outs = [t.detach() for t in tensors[:n]]
         targets = list(tensors[n:])
         for o, t in zip(outs, targets):
-            if not o.is_cuda:
-                raise RuntimeError('MSEProxyLoss runs on the GPU through libsfvos.so (no CPU fallback)')
+            _check_gpu(o, 'MSEProxyLoss')
             if o.dtype != torch.float32 or t.dtype != torch.float32 or o.shape != t.shape:
                 raise RuntimeError('MSEProxyLoss: outputs and targets must be fp32 tensors of equal shape')
         outs = [o if o.is_contiguous() else o.contiguous() for o in outs]

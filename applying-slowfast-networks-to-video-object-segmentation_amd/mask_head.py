@@ -22,8 +22,8 @@ import torch
 from torch import nn
 
 from . import _lib
-from ._heads import _check_gpu, _check_precision, _f32, _pack, _project_bwd, _reduce_rows, _to_nchw, _to_nhwc
-from .module import _DT, _conv_desc, _ptr, _stream
+from ._heads import _check_precision, _pack, _project_bwd, _relu_bwd, _to_nchw, _to_nhwc
+from ._lib import _DT, _check_gpu, _conv_desc, _f32, _ptr, _stream
 
 
 class MaskRCNNHeads(nn.Module):
@@ -62,9 +62,8 @@ class MaskRCNNHeads(nn.Module):
             conv = getattr(self, 'mask_fcn%d' % i)
             d = _conv3x3_desc(dt_id, N, H, W, conv.in_channels, conv.out_channels, relu=1)
             y = torch.empty((N, H, W, conv.out_channels), dtype=tdt, device=x.device)
-            bias = _ptr(conv.bias.detach()) if conv.bias is not None else None
-            _lib.call('sfvos_conv3d', ctypes.byref(d), _ptr(cur), _ptr(self._packed(conv, dt_id, tdt)), bias, _ptr(y),
-                      None, _stream())
+            _lib.call('sfvos_conv3d', ctypes.byref(d), _ptr(cur), _ptr(self._packed(conv, dt_id, tdt)), _ptr(conv.bias),
+                      _ptr(y), None, _stream())
             cur = y
             acts.append(cur)
         return acts if keep else cur
@@ -100,9 +99,8 @@ class MaskRCNNPredictor(nn.Module):
         w = self.conv5_mask.weight
         packed = self._packed(dt_id, tdt)
         y = torch.empty((N, 2 * H, 2 * W, w.shape[1]), dtype=tdt, device=x_nhwc.device)
-        b = self.conv5_mask.bias
-        _lib.call('sfvos_deconv2x2_relu', _ptr(x_nhwc), _ptr(packed), _ptr(b.detach()) if b is not None else None,
-                  _ptr(y), dt_id, N, H, W, w.shape[0], w.shape[1], 1, _stream())
+        _lib.call('sfvos_deconv2x2_relu', _ptr(x_nhwc), _ptr(packed), _ptr(self.conv5_mask.bias), _ptr(y), dt_id, N, H,
+                  W, w.shape[0], w.shape[1], 1, _stream())
         return y
 
     def _logits(self, y_nhwc, labels=None, want_logits=True, want_prob=False):
@@ -118,9 +116,8 @@ class MaskRCNNPredictor(nn.Module):
             lab = labels.to(device=y_nhwc.device, dtype=torch.int64).contiguous()
             if lab.numel() != N:
                 raise RuntimeError('one label per RoI expected')
-        _lib.call('sfvos_mask_logits', _ptr(y_nhwc), dt_id, _ptr(wl), _ptr(conv.bias.detach()) if conv.bias is not None
-                  else None, _ptr(lab) if lab is not None else None, N, H * W, C, K,
-                  _ptr(logits) if logits is not None else None, _ptr(prob) if prob is not None else None, _stream())
+        _lib.call('sfvos_mask_logits', _ptr(y_nhwc), dt_id, _ptr(wl), _ptr(conv.bias), _ptr(lab), N, H * W, C, K,
+                  _ptr(logits), _ptr(prob), _stream())
         return logits, prob
 
     def forward_from_nhwc(self, x_nhwc, labels=None, want_logits=True, want_prob=False):
@@ -217,10 +214,7 @@ class _MaskBranchFn(torch.autograd.Function):
         for i in range(head.n_layers, 0, -1):
             conv = getattr(head, 'mask_fcn%d' % i)
             cin, cout = conv.in_channels, conv.out_channels
-            rrows = lib.sfvos_relu_bwd_rows(M)
-            rpart = torch.empty((rrows, cout), **f32)
-            _lib.call('sfvos_relu_bwd', _ptr(cur), _ptr(acts[i]), _ptr(cur), dt_id, M, cout, _ptr(rpart), _stream())
-            g_b = _reduce_rows(rpart)
+            g_b = _relu_bwd(cur, acts[i], dt_id)
             d = _conv3x3_desc(dt_id, N, H, W, cin, cout)
             g_w = torch.empty(conv.weight.shape, **f32)
             wsz = lib.sfvos_conv3d_wgrad_workspace_bytes(ctypes.byref(d))

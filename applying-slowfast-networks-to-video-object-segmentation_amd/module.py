@@ -19,40 +19,12 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._lib import _DT, _check_gpu, _conv_desc, _f32, _ptr, _stream
 from .plan import SlowFastPlan
 
-_DT = {'fp32': (_lib.F32, torch.float32), 'bf16': (_lib.BF16, torch.bfloat16),
-       # 'fp8': inference only; the four Cin = 256 convs (fast_conv1, slow_conv1-3: 99 % of the forward FLOPs) run on
-       # e4m3 operands, the 32-channel layers and every conv RESULT stay bf16
-       'fp8': (_lib.BF16, torch.bfloat16)}
 # per-level coefficient rows of a BN layer: mean, rstd, scale, shift, var_unbiased, A, B, K, sum dz, sum dz*xhat
 _CF_ROWS = 10
 _MEAN, _RSTD, _SCALE, _SHIFT, _VARU, _CA, _CB, _CK, _SDZ, _SDZX = range(10)
-
-
-def _ptr(t, elem_offset=0):
-    return ctypes.c_void_p(t.data_ptr() + elem_offset * t.element_size())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _conv_desc(dt_id, batch, pyr, kt, taps, c_in, c_out, t_in, x, ld_y, t_alloc=None, t_offset=0, pad_t=0,
-               accumulate=0, relu=0):
-    """sfvos_conv_desc.  x: pitch of the input in elements, or the input tensor itself ([M, ld] ndhwc, or
-    channel-group-major [C/32][M][32] bf16 / [C/64][M][64] e4m3); t_alloc defaults to t_in."""
-    d = _lib.ConvDesc()
-    if torch.is_tensor(x):
-        if x.dim() == 3:
-            d.x_group_stride, x = x.shape[1] * x.shape[2], x.shape[2]
-        else:
-            x = x.shape[-1]
-    d.dtype, d.batch, d.kt, d.taps, d.pyr = dt_id, batch, kt, taps, pyr
-    d.t_in, d.c_in, d.c_out, d.pad_t = t_in, c_in, c_out, pad_t
-    d.t_alloc, d.t_offset = (t_in if t_alloc is None else t_alloc), t_offset
-    d.ld_x, d.ld_y, d.accumulate, d.relu = x, ld_y, accumulate, relu
-    return d
 
 
 def _bn_eval_coeffs(bn, cf, st):
@@ -126,11 +98,10 @@ _NULL = _NullRegion()
 def union_mask(masks, threshold=0.5):
     """Evaluation-side reducer of the reference (code/helpers/davis_evaluate.py:40-42): the union over the
     predicted instance masks [N,1,H,W] (fp32 probabilities, on the GPU) of `mask >= threshold` -> bool [H,W]."""
-    if not masks.is_cuda:
-        raise RuntimeError('union_mask runs on the GPU through libsfvos.so (no CPU fallback)')
+    _check_gpu(masks, 'union_mask')
     if masks.dim() != 4 or masks.shape[1] != 1:
         raise RuntimeError('union_mask expects [N,1,H,W], got %s' % (tuple(masks.shape),))
-    m = masks if (masks.dtype == torch.float32 and masks.is_contiguous()) else masks.float().contiguous()
+    m = _f32(masks)
     H, W = m.shape[2], m.shape[3]
     out = torch.empty((H, W), dtype=torch.uint8, device=m.device)
     _lib.call('sfvos_mask_union', _ptr(m) if m.shape[0] else None, m.shape[0], H * W, float(threshold), _ptr(out),
@@ -310,8 +281,7 @@ class SlowFastLayers(nn.Module):
         amax = None
         for feats in fast_features:
             for v in feats.values():
-                if not v.is_cuda:
-                    raise RuntimeError('calibrate_fp8_scale runs on the GPU through libsfvos.so (no CPU fallback)')
+                _check_gpu(v, 'calibrate_fp8_scale')
                 s = v if v.dtype == torch.float32 else v.float()
                 if amax is None:
                     amax = torch.zeros(1, dtype=torch.float32, device=s.device)
@@ -368,9 +338,7 @@ class SlowFastLayers(nn.Module):
         items = (_lib.PackItem * len(todo))()
         hold = []
         for i, (l2, w2) in enumerate(todo):
-            wc = w2.detach()
-            if wc.dtype != torch.float32 or not wc.is_contiguous():
-                wc = wc.float().contiguous()
+            wc = _f32(w2)
             img = torch.empty(w2.numel(), dtype=tdt, device=w2.device)
             hold.append((wc, img))
             items[i].w, items[i].packed = wc.data_ptr(), img.data_ptr()
@@ -393,11 +361,9 @@ class SlowFastLayers(nn.Module):
         w = conv.weight
         packed = torch.empty(w.numel(), dtype=torch.uint8, device=w.device)
         bd = torch.empty((3, layer.c_out), dtype=torch.float32, device=w.device)
-        wc = w.detach()
-        if wc.dtype != torch.float32 or not wc.is_contiguous():
-            wc = wc.float().contiguous()
-        bc = None if conv.bias is None else conv.bias.detach().float().contiguous()
-        _lib.call('sfvos_pack_weights_fp8', _ptr(wc), _ptr(bc) if bc is not None else None, _ptr(packed), _ptr(bd),
+        wc = _f32(w)
+        bc = None if conv.bias is None else _f32(conv.bias)
+        _lib.call('sfvos_pack_weights_fp8', _ptr(wc), _ptr(bc), _ptr(packed), _ptr(bd),
                   layer.c_out, layer.c_in, layer.kt, layer.taps, act_scale, _stream())
         return packed, bd
 
@@ -498,7 +464,7 @@ class SlowFastLayers(nn.Module):
                 bias = _ptr(bias)
             else:
                 wp = self._packed(l, 'fwd', dt_name)
-                bias = _ptr(conv.bias.detach()) if conv.bias is not None else None
+                bias = _ptr(conv.bias)
             d = _conv_desc(_lib.FP8 if e4m3 else dt_id, B, pyr, l.kt, l.taps, l.c_in, l.c_out, t_in, src, l.c_out,
                            t_alloc, t_off)
             r = _FwdLayer(l, d, _lib.make_levels(shapes, B, l.t_out), src, wp, bias,
@@ -627,8 +593,7 @@ class SlowFastLayers(nn.Module):
             return gb[name]
 
         galloc('out', zero=any(g is None for g in g_merged))
-        gs = [g if (g is None or (g.dtype == torch.float32 and g.is_contiguous())) else g.float().contiguous()
-              for g in g_merged]
+        gs = [g if g is None else _f32(g) for g in g_merged]
         if all(g is not None for g in gs):   # every level in one launch
             _lib.call('sfvos_frames_to_pyramid', _planar_levels(gs), len(gs), _ptr(gb['out']), dt_id, B, 256, 256,
                       _stream())
@@ -734,7 +699,7 @@ class SlowFastLayers(nn.Module):
                     _lib.call('sfvos_bn_bwd_apply', _ptr(dy, l.dst_off), dy.shape[-1], _ptr(raw), l.c_out, _ptr(dx),
                               l.c_out, dt_id, ctypes.byref(lv), l.c_out, _ptr(cf[0, _SCALE]), _ptr(cf[0, _SHIFT]), cs,
                               1 if l.relu else 0, _ptr(cf[0, _CA]), _ptr(cf[0, _CB]), _ptr(cf[0, _CK]),
-                              _ptr(r.bpart) if r.need_b else None, _ptr(cf[0, _SDZ]), _ptr(cf[0, _SDZX]),
+                              _ptr(r.bpart), _ptr(cf[0, _SDZ]), _ptr(cf[0, _SDZX]),
                               _ptr(r.dgamma), _ptr(r.dbeta), sacc if (l.bn + '.weight') in direct else 0, st)
                 grads[l.bn + '.weight'], grads[l.bn + '.bias'] = r.dgamma, r.dbeta
                 if r.need_b:

@@ -10,7 +10,7 @@ keeps working on them); FusedSGD re-homes their storage into a flat buffer so th
 import torch
 
 from . import _lib
-from .module import _ptr, _stream
+from ._lib import _ptr, _stream
 
 
 class FusedSGD(torch.optim.Optimizer):

@@ -17,13 +17,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .module import _ptr, _stream
-
-
-def _check(t, what):
-    if not t.is_cuda:
-        raise RuntimeError('%s runs on the GPU through libsfvos.so (no CPU fallback)' % what)
-    _lib.load()
+from ._lib import _check_gpu, _f32, _ptr, _stream
 
 
 def _workspace(n, dev):
@@ -42,13 +36,11 @@ class _RoIAlignFn(torch.autograd.Function):
         ws = _workspace(K, dev)
         fs = []
         for lvl, (f, sc) in enumerate(zip(feats, scales)):
-            fc = f.detach()
-            if fc.dtype != torch.float32 or not fc.is_contiguous():
-                fc = fc.float().contiguous()
+            fc = _f32(f)
             fs.append(fc)
             B, _, H, W = fc.shape
-            _lib.call('sfvos_roi_align', _ptr(fc), B, C, H, W, _ptr(rois), _ptr(levels) if levels is not None else None,
-                      lvl, K, float(sc), pooled, sampling_ratio, _ptr(ws), _ptr(out), _stream())
+            _lib.call('sfvos_roi_align', _ptr(fc), B, C, H, W, _ptr(rois), _ptr(levels), lvl, K, float(sc), pooled,
+                      sampling_ratio, _ptr(ws), _ptr(out), _stream())
         ctx.rois, ctx.levels, ctx.scales, ctx.pooled, ctx.sr = rois, levels, scales, pooled, sampling_ratio
         ctx.shapes = [tuple(f.shape) for f in fs]
         return out
@@ -56,9 +48,7 @@ class _RoIAlignFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         K = ctx.rois.shape[0]
-        d = dout.detach()
-        if d.dtype != torch.float32 or not d.is_contiguous():
-            d = d.float().contiguous()
+        d = _f32(dout)
         ws = _workspace(K, d.device)
         grads = []
         for lvl, (shape, sc) in enumerate(zip(ctx.shapes, ctx.scales)):
@@ -68,7 +58,7 @@ class _RoIAlignFn(torch.autograd.Function):
             B, C, H, W = shape
             g = torch.empty(shape, dtype=torch.float32, device=d.device)
             _lib.call('sfvos_roi_align_bwd', _ptr(d) if K else None, B, C, H, W, _ptr(ctx.rois) if K else None,
-                      _ptr(ctx.levels) if ctx.levels is not None else None, lvl, K, float(sc), ctx.pooled, ctx.sr,
+                      _ptr(ctx.levels), lvl, K, float(sc), ctx.pooled, ctx.sr,
                       _ptr(ws), _ptr(g), 0, _stream())
             grads.append(g)
         return (None, None, None, None, None) + tuple(grads)
@@ -81,7 +71,7 @@ def roi_align(input, boxes, output_size, spatial_scale=1.0, sampling_ratio=-1, a
         raise NotImplementedError('roi_align: aligned=True is not implemented (torchvision\'s Mask R-CNN uses False)')
     if sampling_ratio <= 0:
         raise NotImplementedError('roi_align: adaptive sampling (sampling_ratio <= 0) is not implemented')
-    _check(input, 'roi_align')
+    _check_gpu(input, 'roi_align')
     pooled = output_size if isinstance(output_size, int) else output_size[0]
     if not isinstance(output_size, int) and output_size[0] != output_size[1]:
         raise NotImplementedError('roi_align: square outputs only')
@@ -136,7 +126,7 @@ class MultiScaleRoIAlign(nn.Module):
         feats = [v for k, v in x.items() if k in self.featmap_names]
         if not feats:
             raise RuntimeError('MultiScaleRoIAlign: none of the feature maps %s present' % (self.featmap_names,))
-        _check(feats[0], 'MultiScaleRoIAlign')
+        _check_gpu(feats[0], 'MultiScaleRoIAlign')
         if self.scales is None or len(self.scales) != len(feats):
             self.setup_scales(feats, image_shapes)
         dev = feats[0].device

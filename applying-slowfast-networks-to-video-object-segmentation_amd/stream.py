@@ -27,7 +27,8 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
-from .module import _CF_ROWS, _DT, _SCALE, _SHIFT, _bn_eval_coeffs, _conv_desc, _ptr, _stream
+from ._lib import _DT, _check_gpu, _conv_desc, _ptr, _stream
+from .module import _CF_ROWS, _SCALE, _SHIFT, _bn_eval_coeffs
 
 
 class _Ring(object):
@@ -64,9 +65,7 @@ class SlowFastStream(object):
         if chunk < 1:
             raise ValueError('chunk must be >= 1')
         w = module.fast_conv1.weight
-        if not w.is_cuda:
-            raise RuntimeError('SlowFastStream runs on the GPU through libsfvos.so (no CPU fallback)')
-        _lib.load()
+        _check_gpu(w, 'SlowFastStream')
         self.chunk = G = int(chunk)
         self.dev = dev = w.device
         self.dt_name = 'bf16' if module.precision == 'fp8' else module.precision   # the stream runs fp8 modules as bf16
@@ -152,7 +151,7 @@ class SlowFastStream(object):
         d.x_frame_stride = d.y_frame_stride = self.FS
         st = _stream()
         raw = self.raw[name]
-        bias = _ptr(conv.bias.detach()) if conv.bias is not None else None
+        bias = _ptr(conv.bias)
         _lib.call('sfvos_conv3d', ctypes.byref(d), _ptr(ring.buf), _ptr(self.m._packed(l, 'fwd', self.dt_name)), bias,
                   _ptr(raw), None, st)
         cf = self.cf[name]

@@ -18,7 +18,8 @@ buffer, and the frames beyond the ends are zero frames that are never read -- no
 from collections import OrderedDict
 
 from . import _lib
-from .module import _DT, RawReuse
+from ._lib import _DT
+from .module import RawReuse
 
 REUSED_LAYERS = ('f1', 's1')
 

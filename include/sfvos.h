@@ -69,7 +69,8 @@ typedef struct sfvos_levels {
  * 300 (round 3) = sfvos_roi_levels / sfvos_roi_align / sfvos_roi_align_bwd (+ workspace query); 301 =
  * sfvos_shift_frames / sfvos_shift_frames_stat_rows (first-layer reuse across consecutive training windows); 302 = the
  * box branch of roi_heads: sfvos_dense and its packers / gradients, sfvos_box_predictor, sfvos_fastrcnn_loss,
- * sfvos_box_decode / _encode, sfvos_detections. */
+ * sfvos_box_decode / _encode, sfvos_detections; 303 = sfvos_relu_bwd takes any whole number of 16-byte chunks per row;
+ * its twin for wide rows (the box head's) is removed. */
 int sfvos_version(void);
 /* sizes[0..n) = sizeof(sfvos_conv_desc), sizeof(sfvos_pyramid), sizeof(sfvos_levels), sizeof(sfvos_mse_table),
  * sizeof(sfvos_bn_running), sizeof(sfvos_pack_item), sizeof(sfvos_planar_level) as THIS library was compiled; returns
@@ -415,8 +416,9 @@ int sfvos_roi_align_bwd(const float* dout, int B, int C, int H, int W, const flo
  * The 3x3 convs: sfvos_conv3d with a sfvos_pack_weights_dgrad image (data gradient) and sfvos_conv3d_wgrad. ---- */
 
 /* ReLU backward + bias gradient partials: dz[m][c] = a[m][c] > 0 ? dy[m][c] : 0 (a == NULL: dz = dy; dz may alias dy or
- * be NULL); col_part (may be NULL): sfvos_relu_bwd_rows(m) rows of [c] fp32, row r = column sums of dz over its 64
- * positions (sum them with sfvos_reduce_rows: the bias gradient of the conv that produced a).  dy, a, dz: [m][c] dtype. */
+ * be NULL); col_part (may be NULL, but not both it and dz): sfvos_relu_bwd_rows(m) rows of [c] fp32, row r = column
+ * sums of dz over its 64 rows (sum them with sfvos_reduce_rows: the bias gradient of the conv or dense layer that
+ * produced a).  dy, a, dz: [m][c] dtype; c: a whole number of 16-byte chunks (4 fp32 / 8 bf16 elements) up to 2^20. */
 int sfvos_relu_bwd_rows(int64_t m);
 int sfvos_relu_bwd(const void* dy, const void* a, void* dz, int dtype, int64_t m, int c, float* col_part,
                    sfvos_stream_t stream);
@@ -478,11 +480,6 @@ int sfvos_dense(const void* x, const void* w_packed, const float* bias, void* y,
  * columns when positions > 1), dz [m][n], both `dtype`; one exact-f32 MFMA chain over the m rows per output. */
 int sfvos_dense_wgrad(const void* x, const void* dz, int dtype, int m, int n, int k, int positions, float* grad_w,
                       int accumulate, sfvos_stream_t stream);
-/* sfvos_relu_bwd for rows of any width: dz[m][c] = a[m][c] > 0 ? dy[m][c] : 0 (a == NULL: dz = dy; dz may alias dy or be
- * NULL); col_part (may be NULL): sfvos_relu_bwd_wide_rows(m) rows of [c] fp32 column sums over 64 rows each. */
-int sfvos_relu_bwd_wide_rows(int m);
-int sfvos_relu_bwd_wide(const void* dy, const void* a, void* dz, int dtype, int m, int c, float* col_part,
-                        sfvos_stream_t stream);
 
 /* FastRCNNPredictor: logits[m][num_classes] = x . w_cls^T + b_cls, deltas[m][4 num_classes] = x . w_box^T + b_box;
  * x [m][c] `dtype`, weights and outputs fp32; num_classes <= 8. */

@@ -1,0 +1,159 @@
+"""What the per-kernel GPU tests (test_gpu_kernels.py, test_gpu_maskhead_kernels.py, test_gpu_boxhead_kernels.py) share:
+pointers and streams for the C ABI, pyramid buffers, guarded outputs, the `lib` fixture and the per-element pass
+criterion; relmax / rel_l2 also serve the module-level GPU tests.
+
+Pass criterion, per element (never max error / max |ref|: a wrong small element hides under a large neighbour there).
+For an output that is a sum of K products, with `ref` and `mag` (the same operation on the absolute values of all
+operands, bias included) both in float64:
+
+    |got - ref|  <=  u_out * |ref|  +  2 * (K + 1) * 2^-22 * mag
+
+u_out = 2^-8 where the kernel stores bf16 (round to nearest of an 8-bit significand), 0 where it stores fp32.  The second
+term is derived, not measured: any order of K fp32 additions rounded to nearest errs by at most K * 2^-24 * mag; the
+factor 4 admits MFMA adders that truncate; the factor 2 carries the accumulation error through the final rounding and
+the bias add (and, where one operand is bf16 and the other fp32, the rounding of each product).  K is the longest chain
+of fp32 additions one product passes through, stated beside each case.  After ReLU the same bound holds with the
+pre-ReLU ref (|relu(a) - relu(b)| <= |a - b|); the ReLU cases here take u_out * |ref| from the post-ReLU ref, which is
+smaller (0 where ref < 0: there only the accumulation term is left).
+
+Transcendental kernels (mask_logits prob, mask_bce_loss, mask_bce_loss_grad): the allowance is 2^-20 (16 fp32 ulps)
+times the float64 sum of the magnitudes of the terms of the kernel's formula.  The 16 is not derived (no ulp bounds for
+expf / log1pf are documented with the toolchain): it stands for three roundings and two device-library calls.  One term
+is added to the magnitude of a sigmoid: 2^-126 / 2^-20, i.e. an absolute 2^-126, because 1 / (1 + expf(-z)) overflows its
+intermediate for z < -88.72, where the result lies below fp32's normal range and carries no relative precision (the
+kernel returns exactly 0 there).  prob is compared twice (check_prob): with the float64 sigmoid of the kernel's own
+returned logits under that bare allowance, and with the float64 sigmoid of the float64 logit, where the allowance also
+carries the distance the derived bound of the logit moves the sigmoid (|sigmoid(z +- zb) - sigmoid(z)|, evaluated, so it
+vanishes at the saturated ends).  Worst observed error / allowance on an MI355X: prob 0.12 against its own logits (2 of
+the 16 ulps) and 0.058 against the float64 logit, loss 0.017, loss gradient 0.23.  Worst observed error / bound of the
+others, per kernel: at most 0.13 where the store is fp32 (the MSE gradient; sums of products at most 0.082), 0.30-0.996
+where it is bf16 (that term is the exact rounding bound: approached, not exceeded; every bf16 store rounds to nearest)."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+TDT = {'fp32': torch.float32, 'bf16': torch.bfloat16}
+PRECS = ['fp32', 'bf16']
+U_OUT = {'fp32': 0.0, 'bf16': 2.0 ** -8}
+U22 = 2.0 ** -22
+TRANS = 2.0 ** -20          # allowance of the transcendental kernels, relative to the magnitudes of their terms
+FLT_MIN = 2.0 ** -126
+GUARD = 64                  # elements in front of and behind every output (keeps 16-byte alignment)
+SENT = -768.0               # exact in bf16
+
+
+@pytest.fixture(scope='module')
+def lib():
+    from sfvos_amd import _lib
+    _lib.check(_lib.load().sfvos_check_device(), 'sfvos_check_device')
+    return _lib
+
+
+def P(t, off=0):
+    return ctypes.c_void_p(t.data_ptr() + off * t.element_size())
+
+
+def S():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def relmax(a, b):
+    a, b = a.double(), b.double()
+    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
+
+
+def rel_l2(a, b):
+    a, b = a.double().flatten(), b.double().flatten()
+    return float((a - b).norm() / b.norm().clamp_min(1e-30))
+
+
+def DT(lib, prec):
+    return lib.F32 if prec == 'fp32' else lib.BF16
+
+
+def rnd(t, prec):
+    """The operand as the kernel sees it, fp32 on the CPU."""
+    return t.bfloat16().float() if prec == 'bf16' else t.float()
+
+
+class Out:
+    """A device output of `shape` between two guard bands, everything sentinel-filled (NaN for workspaces)."""
+
+    def __init__(self, shape, dtype=torch.float32, fill=SENT):
+        self.n = int(np.prod(shape))
+        self.buf = torch.full((self.n + 2 * GUARD,), SENT, dtype=dtype, device='cuda')
+        self.t = self.buf[GUARD:GUARD + self.n].view(shape)
+        if fill != SENT:
+            self.t.fill_(fill)
+
+    def guards_ok(self):
+        b = self.buf
+        return bool((b[:GUARD] == SENT).all()) and bool((b[GUARD + self.n:] == SENT).all())
+
+    def cpu(self):
+        assert self.guards_ok(), 'wrote outside its buffer'
+        return self.t.cpu()
+
+
+def check(name, got, ref, mag, K, u_out):
+    """The per-element criterion of the module docstring; prints the worst error / bound and where it is."""
+    got, ref, mag = got.detach().double().cpu(), ref.detach().double(), mag.detach().double()
+    assert got.shape == ref.shape == mag.shape, (name, got.shape, ref.shape, mag.shape)
+    assert bool(torch.isfinite(got).all()), '%s: %d non-finite elements' % (name, int((~torch.isfinite(got)).sum()))
+    bound = u_out * ref.abs() + 2.0 * (K + 1) * U22 * mag
+    return _ratio(name, (got - ref).abs(), bound)
+
+
+def check_abs(name, got, ref, allow):
+    got, ref, allow = got.detach().double().cpu(), ref.detach().double(), allow.detach().double()
+    assert got.shape == ref.shape == allow.shape, (name, got.shape, ref.shape, allow.shape)
+    assert bool(torch.isfinite(got).all()), '%s: non-finite elements' % name
+    return _ratio(name, (got - ref).abs(), allow)
+
+
+def _ratio(name, err, bound):
+    ratio = torch.where(err == 0, torch.zeros_like(err), err / bound.clamp_min(1e-300))   # 0 / 0 passes, x / 0 fails
+    if ratio.numel() == 0:
+        return 0.0
+    worst = int(ratio.reshape(-1).argmax())
+    w = float(ratio.reshape(-1)[worst])
+    idx = tuple(int(i) for i in np.unravel_index(worst, tuple(ratio.shape))) if ratio.dim() else ()
+    print('%-46s worst error/bound %.4f at %s (%d of %d above)' % (name, w, idx, int((ratio > 1).sum()), ratio.numel()))
+    assert w <= 1.0, '%s: error/bound %.3f at %s, %d of %d elements above the bound' % (
+        name, w, idx, int((ratio > 1).sum()), ratio.numel())
+    return w
+
+
+def make_desc(_lib, prec, B, T, shapes, cin, cout, kt, taps, pad_t, ld_x, ld_y, acc=0, t_alloc=None, t_offset=0):
+    d = _lib.ConvDesc()
+    d.dtype = _lib.F32 if prec == 'fp32' else _lib.BF16
+    d.batch, d.t_in, d.c_in, d.c_out, d.kt, d.taps, d.pad_t = B, T, cin, cout, kt, taps, pad_t
+    d.t_alloc, d.t_offset = (T if t_alloc is None else t_alloc), t_offset
+    d.ld_x, d.ld_y, d.accumulate = ld_x, ld_y, acc
+    d.pyr = _lib.make_pyramid(shapes)
+    return d, T + 2 * pad_t - kt + 1
+
+
+def to_pyr(levels, prec, ld=None, fill=7.0):
+    """list over levels of [B,C,T,H,W] fp32 cpu -> flat pyramid buffer [M, ld] on the device."""
+    C = levels[0].shape[1]
+    ld = ld or C
+    rows = []
+    for x in levels:
+        rows.append(x.permute(0, 2, 3, 4, 1).reshape(-1, C))
+    flat = torch.full((sum(r.shape[0] for r in rows), ld), fill, dtype=torch.float32)
+    flat[:, :C] = torch.cat(rows, 0)
+    return flat.to(TDT[prec]).cuda()
+
+
+def from_pyr(flat, B, C, T, shapes):
+    """flat [M, ld] device -> list of [B,C,T,H,W] fp32 cpu (first C channels)."""
+    out, off = [], 0
+    f = flat.float().cpu()
+    for (H, W) in shapes:
+        n = B * T * H * W
+        out.append(f[off:off + n, :C].reshape(B, T, H, W, C).permute(0, 4, 1, 2, 3))
+        off += n
+    return out

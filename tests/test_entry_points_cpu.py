@@ -247,8 +247,8 @@ REFUSALS = [(e, kw, None) for e, kws in [
                      dict(dtype=FP8)]),
     ('paste_masks', [dict(masks=None), dict(out=None), dict(n=0), dict(mask_size=0), dict(padding=-1),
                      dict(img_w=0)]),
-    ('relu_bwd', [dict(dy=None), dict(m=0), dict(dz=None, col_part=None), dict(c=0), dict(c=36), dict(c=1024),
-                  dict(c=384), dict(dtype=BAD), dict(dtype=FP8)]),
+    ('relu_bwd', [dict(dy=None), dict(m=0), dict(dz=None, col_part=None), dict(c=0), dict(c=36), dict(c=300),
+                  dict(dtype=F32, c=258), dict(c=(1 << 20) + 8), dict(m=1 << 37), dict(dtype=BAD), dict(dtype=FP8)]),
     ('mask_bce_loss', [dict(logits=None), dict(loss=None), dict(n=0), dict(num_classes=0), dict(positions=0)]),
     ('mask_bce_loss_grad', [dict(labels=None), dict(dlogits=None), dict(n=0), dict(positions=-1)]),
     ('mask_logits_bwd', [dict(y=None), dict(part=None), dict(n=0), dict(positions=0), dict(c=96), dict(c=576),

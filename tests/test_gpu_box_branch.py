@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import box_branch_ref as R
+from kernel_util import rel_l2, relmax
 from oracle.roi_align_ref import OracleMultiScaleRoIAlign
 
 pytestmark = pytest.mark.gpu
@@ -23,16 +24,6 @@ DEV = 'cuda:0'
 
 LEVELS = OrderedDict([('0', (48, 80)), ('1', (24, 40)), ('2', (12, 20)), ('3', (6, 10)), ('pool', (3, 5))])
 IMAGE = (192, 320)
-
-
-def relmax(a, b):
-    a, b = a.double(), b.double()
-    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
-
-
-def rel_l2(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
 
 def make(precision, num_classes=2, seed=5, predictor_scale=8.0):

@@ -1,5 +1,5 @@
 """GPU: the box-branch kernels (csrc/dense.hip, csrc/boxes.hip, csrc/project.hip) one by one through the C ABI, each
-against float64 on the operands the kernel sees, under the per-element criterion of tests/test_gpu_maskhead_kernels.py (see its docstring):
+against float64 on the operands the kernel sees, under the per-element criterion of tests/kernel_util.py (its docstring):
 
     |got - ref|  <=  u_out * |ref|  +  2 * (K + 1) * 2^-22 * mag
 
@@ -20,8 +20,7 @@ import torch.nn.functional as F
 
 import box_branch_ref as R
 from test_box_branch_cpu import quarter_pixel_boxes
-from test_gpu_kernels import P, S, TDT
-from test_gpu_maskhead_kernels import DT, PRECS, TRANS, U22, U_OUT, Out, check, check_abs, lib, rnd  # noqa: F401
+from kernel_util import DT, PRECS, TDT, TRANS, U22, U_OUT, Out, P, S, check, check_abs, lib, rnd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -180,32 +179,6 @@ def test_dense_refuses_bad_shapes(lib):
         lib.call('sfvos_pack_dense_fwd', P(x), P(x), lib.F32, 32, 64, 7, S())
     with pytest.raises(RuntimeError, match='bad dtype'):
         lib.call('sfvos_dense', P(x), P(x), None, P(x), 2, 4, 32, 32, 0, None, S())
-
-
-@pytest.mark.parametrize('prec', PRECS)
-@pytest.mark.parametrize('m,c', [(1000, 1024), (1, 32), (130, 96), (64, 300)])
-def test_relu_bwd_wide(lib, prec, m, c):
-    """dz exact (a copy or zero); column sums: 64 rows per block in fp32, the blocks by sfvos_reduce_rows: K = 64 + rows.
-    In place (dz == dy) as the module calls it."""
-    g = torch.Generator().manual_seed(44)
-    a = torch.randn(m, c, generator=g).clamp_min(0)
-    a.view(-1)[::7] = -0.0
-    a.view(-1)[5::53] = -0.25
-    a = rnd(a, prec)
-    dy = rnd(torch.randn(m, c, generator=g), prec)
-    ref = torch.where(a > 0, dy, torch.zeros(()))
-    rows = lib.load().sfvos_relu_bwd_wide_rows(m)
-    assert rows == -(-m // 64)
-    buf, part, red = Out((m, c), TDT[prec]), Out((rows, c), fill=float('nan')), Out((c,))
-    buf.t.copy_(dy.to(TDT[prec]))
-    ad = a.to(TDT[prec]).cuda()
-    lib.call('sfvos_relu_bwd_wide', P(buf.t), P(ad), P(buf.t), DT(lib, prec), m, c, P(part.t), S())
-    lib.call('sfvos_reduce_rows', P(part.t), rows, c, P(red.t), 0, S())
-    torch.cuda.synchronize()
-    assert torch.equal(buf.cpu().float(), ref)
-    assert bool(torch.isfinite(part.cpu()).all())
-    check('relu_bwd_wide %s %dx%d column sums' % (prec, m, c), red.cpu(), ref.double().sum(0), ref.double().abs().sum(0),
-          64 + rows, 0.0)
 
 
 # ---- predictor ----------------------------------------------------------------------------------------------------------

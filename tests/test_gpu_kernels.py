@@ -9,65 +9,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from kernel_util import TDT, P, S, from_pyr, lib, make_desc, relmax, to_pyr  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 TOL = {'fp32': 1e-4, 'bf16': 2e-2}
-TDT = {'fp32': torch.float32, 'bf16': torch.bfloat16}
-
-
-@pytest.fixture(scope='module')
-def lib():
-    from sfvos_amd import _lib
-    lib = _lib.load()
-    _lib.check(lib.sfvos_check_device(), 'sfvos_check_device')
-    return _lib
-
-
-def P(t, off=0):
-    return ctypes.c_void_p(t.data_ptr() + off * t.element_size())
-
-
-def S():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def relmax(a, b):
-    a, b = a.double(), b.double()
-    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
-
-
-def make_desc(_lib, prec, B, T, shapes, cin, cout, kt, taps, pad_t, ld_x, ld_y, acc=0, t_alloc=None, t_offset=0):
-    d = _lib.ConvDesc()
-    d.dtype = _lib.F32 if prec == 'fp32' else _lib.BF16
-    d.batch, d.t_in, d.c_in, d.c_out, d.kt, d.taps, d.pad_t = B, T, cin, cout, kt, taps, pad_t
-    d.t_alloc, d.t_offset = (T if t_alloc is None else t_alloc), t_offset
-    d.ld_x, d.ld_y, d.accumulate = ld_x, ld_y, acc
-    d.pyr = _lib.make_pyramid(shapes)
-    return d, T + 2 * pad_t - kt + 1
-
-
-def to_pyr(levels, prec, ld=None, fill=7.0):
-    """list over levels of [B,C,T,H,W] fp32 cpu -> flat pyramid buffer [M, ld] on the device."""
-    C = levels[0].shape[1]
-    ld = ld or C
-    rows = []
-    for x in levels:
-        rows.append(x.permute(0, 2, 3, 4, 1).reshape(-1, C))
-    flat = torch.full((sum(r.shape[0] for r in rows), ld), fill, dtype=torch.float32)
-    flat[:, :C] = torch.cat(rows, 0)
-    return flat.to(TDT[prec]).cuda()
-
-
-def from_pyr(flat, B, C, T, shapes):
-    """flat [M, ld] device -> list of [B,C,T,H,W] fp32 cpu (first C channels)."""
-    out, off = [], 0
-    f = flat.float().cpu()
-    for (H, W) in shapes:
-        n = B * T * H * W
-        out.append(f[off:off + n, :C].reshape(B, T, H, W, C).permute(0, 4, 1, 2, 3))
-        off += n
-    return out
-
 
 CONV_CASES = [
     # B  T   shapes                      cin cout kt taps

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_util import rel_l2, relmax
 from oracle.mask_head_ref import OracleMaskBranch
 from oracle.mask_head_ref import maskrcnn_inference as ref_inference
 from oracle.mask_head_ref import maskrcnn_loss as ref_loss
@@ -17,11 +18,6 @@ from oracle.mask_head_ref import paste_masks_in_image as ref_paste
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
-
-
-def relmax(a, b):
-    a, b = a.double(), b.double()
-    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
 
 
 def make(precision):
@@ -169,10 +165,6 @@ def test_mask_branch_training_step_matches_the_oracle(precision):
     tol_l = 1e-5 if precision == 'fp32' else 2e-2
     lv, lr = float(loss.detach()), float(loss_ref.detach())
     assert abs(lv - lr) <= tol_l * abs(lr), (lv, lr)
-
-    def rel_l2(a, b):
-        a, b = a.double().flatten(), b.double().flatten()
-        return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
     worst = 0.0
     names = dict(o.named_parameters())

@@ -2,32 +2,7 @@
 test_gpu_kernels.py, each against the plain torch operation in float64 on the CPU on the operands the kernel sees
 (bf16: rounded to bf16 first, then widened).
 
-Pass criterion, per element (never max error / max |ref|: a wrong small element hides under a large neighbour there).
-For an output that is a sum of K products, with `ref` and `mag` (the same operation on the absolute values of all
-operands, bias included) both in float64:
-
-    |got - ref|  <=  u_out * |ref|  +  2 * (K + 1) * 2^-22 * mag
-
-u_out = 2^-8 where the kernel stores bf16 (round to nearest of an 8-bit significand), 0 where it stores fp32.  The second
-term is derived, not measured: any order of K fp32 additions rounded to nearest errs by at most K * 2^-24 * mag; the
-factor 4 admits MFMA adders that truncate; the factor 2 carries the accumulation error through the final rounding and
-the bias add (and, where one operand is bf16 and the other fp32, the rounding of each product).  K is the longest chain
-of fp32 additions one product passes through, stated beside each case.  After ReLU the same bound holds with the
-pre-ReLU ref (|relu(a) - relu(b)| <= |a - b|); the ReLU cases here take u_out * |ref| from the post-ReLU ref, which is
-smaller (0 where ref < 0: there only the accumulation term is left).
-
-Transcendental kernels (mask_logits prob, mask_bce_loss, mask_bce_loss_grad): the allowance is 2^-20 (16 fp32 ulps)
-times the float64 sum of the magnitudes of the terms of the kernel's formula.  The 16 is not derived (no ulp bounds for
-expf / log1pf are documented with the toolchain): it stands for three roundings and two device-library calls.  One term
-is added to the magnitude of a sigmoid: 2^-126 / 2^-20, i.e. an absolute 2^-126, because 1 / (1 + expf(-z)) overflows its
-intermediate for z < -88.72, where the result lies below fp32's normal range and carries no relative precision (the
-kernel returns exactly 0 there).  prob is compared twice (check_prob): with the float64 sigmoid of the kernel's own
-returned logits under that bare allowance, and with the float64 sigmoid of the float64 logit, where the allowance also
-carries the distance the derived bound of the logit moves the sigmoid (|sigmoid(z +- zb) - sigmoid(z)|, evaluated, so it
-vanishes at the saturated ends).  Worst observed error / allowance on an MI355X: prob 0.12 against its own logits (2 of
-the 16 ulps) and 0.058 against the float64 logit, loss 0.017, loss gradient 0.23.  Worst observed error / bound of the
-others, per kernel: at most 0.13 where the store is fp32 (the MSE gradient; sums of products at most 0.082), 0.30-0.996
-where it is bf16 (that term is the exact rounding bound: approached, not exceeded; every bf16 store rounds to nearest).
+Pass criterion: the per-element bound of tests/kernel_util.py (its docstring), K stated beside each case.
 
 Every output buffer has a guard band in front and behind (and sentinel-filled unused columns where it is pitched), the
 body is sentinel-filled too, so an unwritten element shows as an error; workspaces and partial rows are NaN-filled.  No
@@ -40,81 +15,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from test_gpu_kernels import P, S, TDT, make_desc, to_pyr
+from kernel_util import (DT, FLT_MIN, PRECS, SENT, TDT, TRANS, U22, U_OUT, Out, P, S, check, check_abs,  # noqa: F401
+                         lib, make_desc, rnd, to_pyr)
 
 pytestmark = pytest.mark.gpu
-
-PRECS = ['fp32', 'bf16']
-U_OUT = {'fp32': 0.0, 'bf16': 2.0 ** -8}
-U22 = 2.0 ** -22
-TRANS = 2.0 ** -20          # allowance of the transcendental kernels, relative to the magnitudes of their terms
-FLT_MIN = 2.0 ** -126
-GUARD = 64                  # elements in front of and behind every output (keeps 16-byte alignment)
-SENT = -768.0               # exact in bf16
-
-
-@pytest.fixture(scope='module')
-def lib():
-    from sfvos_amd import _lib
-    _lib.check(_lib.load().sfvos_check_device(), 'sfvos_check_device')
-    return _lib
-
-
-def DT(lib, prec):
-    return lib.F32 if prec == 'fp32' else lib.BF16
-
-
-def rnd(t, prec):
-    """The operand as the kernel sees it, fp32 on the CPU."""
-    return t.bfloat16().float() if prec == 'bf16' else t.float()
-
-
-class Out:
-    """A device output of `shape` between two guard bands, everything sentinel-filled (NaN for workspaces)."""
-
-    def __init__(self, shape, dtype=torch.float32, fill=SENT):
-        self.n = int(np.prod(shape))
-        self.buf = torch.full((self.n + 2 * GUARD,), SENT, dtype=dtype, device='cuda')
-        self.t = self.buf[GUARD:GUARD + self.n].view(shape)
-        if fill != SENT:
-            self.t.fill_(fill)
-
-    def guards_ok(self):
-        b = self.buf
-        return bool((b[:GUARD] == SENT).all()) and bool((b[GUARD + self.n:] == SENT).all())
-
-    def cpu(self):
-        assert self.guards_ok(), 'wrote outside its buffer'
-        return self.t.cpu()
-
-
-def check(name, got, ref, mag, K, u_out):
-    """The per-element criterion of the module docstring; prints the worst error / bound and where it is."""
-    got, ref, mag = got.detach().double().cpu(), ref.detach().double(), mag.detach().double()
-    assert got.shape == ref.shape == mag.shape, (name, got.shape, ref.shape, mag.shape)
-    assert bool(torch.isfinite(got).all()), '%s: %d non-finite elements' % (name, int((~torch.isfinite(got)).sum()))
-    bound = u_out * ref.abs() + 2.0 * (K + 1) * U22 * mag
-    return _ratio(name, (got - ref).abs(), bound)
-
-
-def check_abs(name, got, ref, allow):
-    got, ref, allow = got.detach().double().cpu(), ref.detach().double(), allow.detach().double()
-    assert got.shape == ref.shape == allow.shape, (name, got.shape, ref.shape, allow.shape)
-    assert bool(torch.isfinite(got).all()), '%s: non-finite elements' % name
-    return _ratio(name, (got - ref).abs(), allow)
-
-
-def _ratio(name, err, bound):
-    ratio = torch.where(err == 0, torch.zeros_like(err), err / bound.clamp_min(1e-300))   # 0 / 0 passes, x / 0 fails
-    if ratio.numel() == 0:
-        return 0.0
-    worst = int(ratio.reshape(-1).argmax())
-    w = float(ratio.reshape(-1)[worst])
-    idx = tuple(int(i) for i in np.unravel_index(worst, tuple(ratio.shape))) if ratio.dim() else ()
-    print('%-46s worst error/bound %.4f at %s (%d of %d above)' % (name, w, idx, int((ratio > 1).sum()), ratio.numel()))
-    assert w <= 1.0, '%s: error/bound %.3f at %s, %d of %d elements above the bound' % (
-        name, w, idx, int((ratio > 1).sum()), ratio.numel())
-    return w
 
 
 # ---- ConvTranspose2d(2, 2, 0): packers, forward, data gradient, weight gradient ---------------------------------------
@@ -427,10 +331,20 @@ def test_mask_logits_bwd(lib, prec, case, relu):
 
 # ---- ReLU backward + column sums ---------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize('prec,c', [('fp32', 4), ('fp32', 32), ('fp32', 256), ('bf16', 8), ('bf16', 64), ('bf16', 512)])
-@pytest.mark.parametrize('m', [1, 63, 64, 65, 1764])
+# One column block (up to 64 16-byte chunks per row) of a power-of-two chunk count (1, 8 and 64): the mask head's path
+RELU_CASES = [(prec, c, m) for m in (1, 63, 64, 65, 1764)
+              for prec, c in (('fp32', 4), ('fp32', 32), ('fp32', 256), ('bf16', 8), ('bf16', 64), ('bf16', 512))]
+# Tiled over columns: 65 chunks = a second block of one chunk (fp32 260, bf16 520); blocks that are no power of two,
+# with idle threads: 24 / 12 and 48 chunks (96, bf16 384), 75 = 64 + 11 (fp32 300); the box head's 1024 = 4 / 2 blocks
+RELU_CASES += [(prec, c, m) for m in (1, 63, 64, 65, 130)
+               for prec, c in (('fp32', 260), ('bf16', 520), ('fp32', 96), ('bf16', 96), ('bf16', 384), ('fp32', 300),
+                               ('fp32', 1024), ('bf16', 1024))]
+RELU_CASES += [('fp32', 1024, 1000), ('bf16', 1024, 1000), ('bf16', 32, 1)]
+
+
+@pytest.mark.parametrize('prec,c,m', RELU_CASES, ids=['%d-%s-%d' % (m, prec, c) for prec, c, m in RELU_CASES])
 def test_relu_bwd(lib, prec, c, m):
-    """1, 8 and 64 16-byte chunks per row.  dz is exact; a partial row sums at most 64 positions (K = 64), the total
+    """dz is exact; a partial row sums at most 64 positions (K = 64), the total
     behind sfvos_reduce_rows has K = 64 + rows.  a holds 0, -0.0 and NaN: `a > 0` is false there, the gradient is 0 (what
     torch.where(a > 0, dy, 0) gives in float64).  Variants: all outputs, a = NULL, dz = NULL, col_part = NULL, in place."""
     g = torch.Generator().manual_seed(41)

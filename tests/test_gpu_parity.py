@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from golden_util import (BIG_LEVELS, CONFIGS, SMALL_LEVELS, clip_inputs, load_case, max_rel_err, rel_err, sample_idx)
+from kernel_util import rel_l2
 from oracle.closed_form import closed_form_features, closed_form_state_dict
 from oracle.slowfast_ref import OracleSlowFastLayers, proxy_loss
 
@@ -799,10 +800,6 @@ def test_c1_eight_centre_frames_trajectory_matches_the_oracle(fused, precision):
             opt.step(); opt_r.step()
             opt.zero_grad(); opt_r.zero_grad()
     torch.cuda.synchronize()
-
-    def rel_l2(a, b):
-        a, b = a.double().flatten(), b.double().flatten()
-        return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
     zero_grad_bias = ('conv1.bias', 'conv2.bias', 'conv3.bias')   # conv bias in front of a train-mode BN: gradient 0
     worst_u = worst_m = worst_s = 0.0

@@ -12,16 +12,12 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_util import relmax
 from oracle.roi_align_ref import OracleMultiScaleRoIAlign
 from oracle.roi_align_ref import roi_align as ref_roi_align
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
-
-
-def relmax(a, b):
-    a, b = a.double(), b.double()
-    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
 
 
 ROIS = torch.tensor([[0, 10.3, 20.7, 110.2, 90.5],       # ordinary

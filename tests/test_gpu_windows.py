@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from golden_util import SMALL_LEVELS, max_rel_err, rel_err
+from kernel_util import rel_l2
 from oracle.closed_form import closed_form_features, closed_form_state_dict, slice_slow
 from oracle.slowfast_ref import OracleSlowFastLayers, proxy_loss
 
@@ -170,11 +171,6 @@ def _gpu_trajectory(sp, fp, precision, video, reuse, fused):
     return steps, params, stats
 
 
-def _rel_l2(a, b):
-    a, b = a.double().flatten(), b.double().flatten()
-    return float((a - b).norm() / b.norm().clamp_min(1e-30))
-
-
 # ---------------------------------------------------------------------------------------------- 2. the training loop
 _ORACLE = {}
 
@@ -232,9 +228,9 @@ def test_reference_training_loop_matches_oracle_and_plain_path(sp, fp, precision
                     e = rel_err(gr.numpy(), r['grad'][name].numpy())
                     e_plain = rel_err(pl['grad'][name].numpy(), r['grad'][name].numpy())
                     worst['grad'], worst['plain_grad'] = max(worst['grad'], e), max(worst['plain_grad'], e_plain)
-        eu = max(_rel_l2(params[n] - p0[n], ref_params[n] - p0[n]) for n in params if not n.endswith(ZERO_GRAD_BIAS))
+        eu = max(rel_l2(params[n] - p0[n], ref_params[n] - p0[n]) for n in params if not n.endswith(ZERO_GRAD_BIAS))
         es = max(max_rel_err(stats[n].numpy(), ref_stats[n].numpy()) for n in stats)
-        eu_plain = max(_rel_l2(plain[1][n] - p0[n], ref_params[n] - p0[n]) for n in params
+        eu_plain = max(rel_l2(plain[1][n] - p0[n], ref_params[n] - p0[n]) for n in params
                        if not n.endswith(ZERO_GRAD_BIAS))
         es_plain = max(max_rel_err(plain[2][n].numpy(), ref_stats[n].numpy()) for n in stats)
         print('(%d,%d) %s %s: vs oracle maps %.2e loss %.2e grads %.2e updates %.2e running %.2e | vs plain maps %.2e '
@@ -341,7 +337,7 @@ def test_full_size_bf16_two_consecutive_centres():
         del m, win
     (o1, l1, g1), (o0, l0, g0) = res
     eo = max(float((o1[k] - o0[k]).abs().max() / o0[k].abs().max()) for k in o0)
-    e2 = max(_rel_l2(o1[k], o0[k]) for k in o0)
+    e2 = max(rel_l2(o1[k], o0[k]) for k in o0)
     el = abs(l1 - l0) / abs(l0)
     print('full size (4,32) bf16, reuse vs plain: maps max %.2e of the scale, rel-L2 %.2e, loss %.2e' % (eo, e2, el))
     assert e2 < 1e-2 and eo < gates['out'] and el < gates['loss']
@@ -350,7 +346,7 @@ def test_full_size_bf16_two_consecutive_centres():
         if k.endswith(ZERO_GRAD_BIAS):
             assert float(g1[k].abs().max()) < gates['g3'][1] * gscale, k
             continue
-        e2, emax = _rel_l2(g1[k], g0[k]), float((g1[k] - g0[k]).abs().max() / g0[k].abs().max())
+        e2, emax = rel_l2(g1[k], g0[k]), float((g1[k] - g0[k]).abs().max() / g0[k].abs().max())
         gate = gates['g3'] if k.startswith(LAYER3) else gates['g12']
         print('  grad %-18s rel-L2 %.2e, max / scale %.2e (gate %s)' % (k, e2, emax, gate))
         assert e2 < gate[0] and emax < gate[1], (k, e2, emax)
