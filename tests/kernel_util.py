@@ -1,6 +1,6 @@
-"""What the per-kernel GPU tests (test_gpu_kernels.py, test_gpu_maskhead_kernels.py, test_gpu_boxhead_kernels.py) share:
-pointers and streams for the C ABI, pyramid buffers, guarded outputs, the `lib` fixture and the per-element pass
-criterion; relmax / rel_l2 also serve the module-level GPU tests.
+"""What the per-kernel GPU tests (test_gpu_kernels.py, test_gpu_maskhead_kernels.py, test_gpu_boxhead_kernels.py,
+test_gpu_bn_kernels.py) share: pointers and streams for the C ABI, pyramid buffers, level tables, guarded outputs, the
+`lib` fixture and the per-element pass criterion; relmax / rel_l2 also serve the module-level GPU tests.
 
 Pass criterion, per element (never max error / max |ref|: a wrong small element hides under a large neighbour there).
 For an output that is a sum of K products, with `ref` and `mag` (the same operation on the absolute values of all
@@ -27,7 +27,40 @@ carries the distance the derived bound of the logit moves the sigmoid (|sigmoid(
 vanishes at the saturated ends).  Worst observed error / allowance on an MI355X: prob 0.12 against its own logits (2 of
 the 16 ulps) and 0.058 against the float64 logit, loss 0.017, loss gradient 0.23.  Worst observed error / bound of the
 others, per kernel: at most 0.13 where the store is fp32 (the MSE gradient; sums of products at most 0.082), 0.30-0.996
-where it is bf16 (that term is the exact rounding bound: approached, not exceeded; every bf16 store rounds to nearest)."""
+where it is bf16 (that term is the exact rounding bound: approached, not exceeded; every bf16 store rounds to nearest).
+
+The BatchNorm chain (test_gpu_bn_kernels.py, references in bn_ref.py) adds three cases of the same criterion.
+
+Exactly summable operands (check_exact): where the chain is long -- every statistics row of a conv, any level of more
+than a few thousand positions -- the K * mag term exceeds what one dropped or doubled position changes and proves
+nothing.  There the operands are small integers and power-of-two coefficients for which every partial sum, in any order
+and any partition into rows, is an integer multiple of a stated power of two below 2^24 of it: every fp32 addition is
+exact, the accumulation term is derived to be ZERO, and the test asserts got == ref (u_out = 0 for statistics and
+partial rows, which are sums of the unrounded fp32 values on the bf16 path too; a bf16 y holds |v| <= 256 exactly).
+The precondition is asserted on the float64 reference (test_bn_ref_cpu.py: integers or the stated dyadic multiple,
+every mag below 2^24, per level sum |v| and sum v^2 below 2^24).  A failure by a non-integer or by less than one product
+would be a finding about the adder, not about the test.
+
+Double arithmetic (bn_finalize, bn_bwd_finalize: sums, division, square root in double, cast to float): the allowance
+is the cast, 2^-24 * |ref|, plus 2^-45 times the float64 magnitude of the terms of the kernel's formula.  For rstd =
+1 / sqrt(var + eps) the second part is the reference evaluated at var +- dv, dv = 2^-45 * (s2 / count + m^2), as
+check_prob evaluates the sigmoid at z +- zb; the reference uses the kernel's formula (s2 / count - m^2, clamped at 0) on
+the same fp32 rows summed in float64.  The 2^-45 is not derived: it stands for a few hundred double ulps of the device's
+double sqrt and divide and of the order of the double sums, for which the toolchain documents no bound.  scale and
+shift, fp32 arithmetic on the kernel's own rstd and mean, are compared twice as prob is: with those returned values
+(K = 0 / K = 1) and with float64 throughout, the allowances of rstd and mean carried through.
+
+ReLU masks: the kernels define the mask as fp32 `x * scale + shift > 0`, possibly one FMA; float64 can disagree where
+that value is within rounding of zero.  Such elements (|x sc + sh| <= 2^-22 (|x sc| + |sh|) and not exactly 0) are not
+left out: they get dy = 0 in the input, so both outcomes give the same result (at most 0.1 % of a channel, asserted on
+the CPU; none occurs for the committed seeds).  Exact zeros are not ambiguous: the gradient there is 0.
+
+Worst observed error / bound of the BatchNorm chain on an MI355X, per kernel: every exact case equal (24 conv cases with
+y, S1, S2 per level, the ReLU y, 7 shift cases, the 512 * 512 + 37 level of bn_bwd_reduce and bn_bwd_apply); bn_finalize
+0.996 and bn_bwd_finalize 0.9994 (the cast is the exact rounding bound: approached, not exceeded), scale / shift of
+bn_finalize 0.12 / 0.061 against the kernel's own rstd and mean, 0.18 / 0.092 against float64; bn_running_update 0.048;
+bn_apply 0.062 (fp32), 0.996 (bf16); bn_bwd_reduce 0.0045; bn_bwd_apply dx 0.087 (fp32), 0.996 (bf16), its bias rows
+0.0025, dgamma / dbeta 0.093."""
 import ctypes
 
 import numpy as np
@@ -111,6 +144,34 @@ def check_abs(name, got, ref, allow):
     assert got.shape == ref.shape == allow.shape, (name, got.shape, ref.shape, allow.shape)
     assert bool(torch.isfinite(got).all()), '%s: non-finite elements' % name
     return _ratio(name, (got - ref).abs(), allow)
+
+
+def check_exact(name, got, ref):
+    """Exactly summable operands (docstring): the accumulation term of the criterion is derived to be zero, so got == ref.
+    Prints how many elements differ and by how much at most."""
+    got, ref = got.detach().double().cpu(), ref.detach().double()
+    assert got.shape == ref.shape, (name, got.shape, ref.shape)
+    diff = (got - ref).abs()
+    bad = ~(got == ref)      # NaN differs
+    n = int(bad.sum())
+    where = ()
+    if n:
+        worst = int(torch.where(bad, diff.nan_to_num(float('inf')), -torch.ones_like(diff)).reshape(-1).argmax())
+        where = tuple(int(i) for i in np.unravel_index(worst, tuple(diff.shape))) if diff.dim() else ()
+    print('%-46s exact: %d of %d differ%s' % (name, n, got.numel(), '' if not n else ', most at %s: got %r, ref %r' % (
+        where, float(got[where]), float(ref[where]))))
+    assert n == 0, '%s: %d of %d elements differ from float64, most at %s: got %r, ref %r' % (
+        name, n, got.numel(), where, float(got[where]), float(ref[where]))
+    return 0.0
+
+
+def levels(_lib, ms):
+    """sfvos_levels of a flat pyramid buffer with ms[l] positions in level l."""
+    lv = _lib.Levels()
+    lv.n_levels = len(ms)
+    for i, m in enumerate(ms):
+        lv.m[i] = m
+    return lv
 
 
 def _ratio(name, err, bound):
