@@ -41,6 +41,7 @@ template <> struct Elt<SFVOS_FP8> {   // OCP e4m3 bytes; conversions go through 
 };
 // element type a conv writes for a given operand type: fp8 operands -> bf16 results
 template <int DT> struct YOf { static constexpr int DTY = DT == SFVOS_FP8 ? SFVOS_BF16 : DT; };
+typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
 // One MFMA "step" consumes one 16-B chunk per lane of A and of B: lane half h (lane>>5)
@@ -67,6 +68,11 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
 }
 
 __device__ __forceinline__ u32x4 lds_read16(const void* p) { return *(const u32x4*)p; }
+// two ds_read_b128 -> one 32-byte e4m3 MFMA operand (a register octet)
+__device__ __forceinline__ i32x8 read8(const char* lo, const char* hi) {
+  const i32x4 l = __builtin_bit_cast(i32x4, lds_read16(lo)), h = __builtin_bit_cast(i32x4, lds_read16(hi));
+  return __builtin_shufflevector(l, h, 0, 1, 2, 3, 4, 5, 6, 7);
+}
 
 // LDS-DMA through a buffer descriptor, as one asm statement: buffer_load_dwordx4 ... offen lds.
 // Why not __builtin_amdgcn_raw_ptr_buffer_load_lds: hipcc tracks that builtin as an LDS write and, when it cannot
@@ -77,7 +83,6 @@ __device__ __forceinline__ u32x4 lds_read16(const void* p) { return *(const u32x
 //   base/records: descriptor of the source (wave-uniform); voff: this lane's byte offset, >= records reads zeros;
 //   lds_offset: wave-uniform byte offset inside the workgroup's LDS allocation (kernels here have dynamic LDS only, so
 //   `ptr - smem` is the LDS address), lane i lands at +16 i.
-typedef __attribute__((ext_vector_type(4))) int i32x4;
 __device__ __forceinline__ void lds_dma16(const void* base, int records, unsigned voff, unsigned lds_offset) {
   const unsigned long long b = (unsigned long long)base;
   i32x4 rs;

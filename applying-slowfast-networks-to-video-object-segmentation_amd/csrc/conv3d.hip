@@ -108,8 +108,135 @@ struct ConvCfg {
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
 
-// CIN: compile-time c_in (0 = runtime).  The 256-channel instances get their own symbol, so the dominant
-// launches (fast_conv1 forward) are identifiable in a rocprofv3 kernel trace, and a constant chunk count.
+// ---- shared by both device bodies (conv3d_body, fs_body): everything that is not their MFMA loop ------------
+
+// Temporal taps [lo, hi] that can touch a real frame for the block of output frames [tb0, tb0 + more]: with temporal
+// zero padding (data-gradient convs, pad_t = kt-1) most (dt, frame) pairs of a block are padding -- the kernels skip
+// them, and make_plan counts what is left.  Empty when hi < lo.  (`more` is the frame count minus one on purpose:
+// the kernels pass the constant TT - 1; with the count as the argument hipcc unswitches the fp32 wide loops differently.)
+struct TapRange { int lo, hi; };
+__host__ __device__ __forceinline__ TapRange live_taps(int pad_t, int kt, int t_in, int tb0, int more) {
+  const int lo = pad_t - tb0 - more, hi = pad_t - tb0 + t_in - 1;
+  return TapRange{0 > lo ? 0 : lo, kt - 1 < hi ? kt - 1 : hi};
+}
+
+// ---- staging: buffer_load ... lds (LDS-DMA through a buffer descriptor).  A copy is (descriptor of the frame /
+// weight slice, per-lane byte offset fixed for the whole kernel): padding pixels and frames outside the clip
+// carry an out-of-range offset / an empty descriptor and the hardware range check writes zeros for them, so a
+// piece costs two scalar instructions and no vector ALU work.  Pieces are whole wave-instructions (64 slots);
+// wave w owns pieces w, w+8, w+16 of an image.
+struct Dma {
+  const char* xsrc; char* xb; int xrec; bool do_x;
+  const char* wsrc; char* wb; int wrec; bool do_w;
+};
+
+// C: the body's Cfg (ring slots R, image sizes, BN, HC); weight slices are [TPS of TAPS taps][4 chunks][BN];
+// SWZ2: the swizzle of the 16x16x32 fragments of the frame-split kernel (see the constructor).
+template <class C, int HALO, int TAPS, int TPS, bool SWZ2>
+struct Staging {
+  static constexpr int XWP = (C::X_SLOTS + 63) / 64, WWP = (C::W_SLOTS + 63) / 64;  // wave-pieces per frame / weight slice
+  static constexpr int NWV = C::NWAVES;
+  static constexpr int NX = (XWP + NWV - 1) / NWV, NW = (WWP + NWV - 1) / NWV, NPIECE = NX + NW;
+  static constexpr unsigned OOB = 0x80000000u;
+  static_assert(C::X_BYTES >= XWP * 1024 && C::W_BYTES >= WWP * 1024, "staging images hold whole wave-pieces");
+  const ConvArgs& a;
+  unsigned xo[NX], wo[NW];  // per-lane source offsets of the pieces of a frame / a weight slice
+  char* ring;               // C::R halo tiles
+  char* wbase;              // two weight buffers
+  const char* xclip;        // frame 0 of this clip inside the x buffer (t_alloc frames per clip, the conv's window starts at t_offset)
+  long long xfs_bytes;      // bytes between consecutive frames of this level
+  int frame_bytes, lds_wave_off, wv, tb0, n0;
+
+  __device__ __forceinline__ Staging(const ConvArgs& a_, char* smem, int tid, int wv_, int lvl, int b, int h0, int w0,
+                                     int n0_, int tb0_) : a(a_) {
+    const int H = a.lv.H[lvl], W = a.lv.W[lvl];
+    ring = smem; wbase = smem + C::R * C::X_BYTES;
+    xclip = a.x + (a.lv.xpos[lvl] + b * a.lv.xbs[lvl]) * a.x_pitch_bytes;
+    xfs_bytes = a.lv.xfs[lvl] * a.x_pitch_bytes;
+    frame_bytes = (int)((long long)H * W * a.x_pitch_bytes);
+    wv = wv_; lds_wave_off = wv * 1024; tb0 = tb0_; n0 = n0_;
+#pragma unroll
+    for (int it = 0; it < NX; ++it) {
+      // pixel-major halo image: slot = (row*HC + col)*4 + (chunk ^ swz(col)).  Four consecutive lanes copy the four
+      // 16-byte chunks of ONE pixel (a 64-byte run of global memory), so the copy is coalesced; the XOR spreads
+      // the 16 lanes of a ds_read_b128 group over all 64 banks: swz = (col>>2)&3 for the 32x32 fragments (same
+      // chunk, 16 columns), 2*((col>>2)&1) for the 16x16x32 ones of the frame-split kernel (two chunks x 8 columns
+      // per group).
+      const int sl = it * C::NTHREADS + tid;
+      const int cq = sl & 3, rc = sl >> 2, col = rc % C::HC, row = rc / C::HC;
+      const int j = cq ^ (SWZ2 ? 2 * ((col >> 2) & 1) : ((col >> 2) & 3));
+      const int h = h0 + row - HALO, w = w0 + col - HALO;
+      const bool ok = sl < C::X_SLOTS && (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
+      xo[it] = ok ? (unsigned)(((long long)h * W + w) * a.x_pitch_bytes + j * 16) : OOB;
+    }
+#pragma unroll
+    for (int it = 0; it < NW; ++it) {
+      const int sl = it * C::NTHREADS + tid;
+      const int tj = sl / C::BN, n = sl - tj * C::BN;  // tj = tap_local*4 + chunk
+      wo[it] = (sl < C::W_SLOTS && n0 + n < a.c_out) ? (unsigned)((tj * a.c_out + n) * 16) : OOB;
+    }
+  }
+
+  static __device__ __forceinline__ int wrap(int sl) { return sl >= C::R ? sl - C::R : sl; }
+  __device__ __forceinline__ void prep_frame(Dma& d, int cc, int i, int slot) const {  // halo tile of input frame i, chunk cc -> ring slot
+    const int t = tb0 - a.pad_t + i, ft = a.t_offset + t;  // frame of the conv's window / of the x buffer
+    // outside the window (temporal padding) or outside the buffer (zero frames "by pointer", model.py:215-225):
+    // an empty descriptor, the copy writes zeros.  (pyramid NDHWC: the chunk offset sits inside the pixel)
+    const bool t_ok = (unsigned)t < (unsigned)a.t_in && (unsigned)ft < (unsigned)a.t_alloc;
+    d.do_x = true;
+    d.xrec = t_ok ? frame_bytes - (a.x_pitch_bytes > 64 ? cc * 64 : 0) : 0;
+    d.xb = ring + slot * C::X_BYTES + lds_wave_off;
+    d.xsrc = xclip + (long long)(t_ok ? ft : 0) * xfs_bytes + cc * a.x_chunk_bytes;
+  }
+  __device__ __forceinline__ void prep_w(Dma& d, int cc, int dt, int tg, int s) const {  // weight slice of stage s: [TPS taps][4 chunks][BN]
+    d.do_w = true;
+    d.wb = wbase + (s & 1) * C::W_BYTES + lds_wave_off;
+    d.wsrc = a.wp + (((long long)(cc * a.kt + dt) * TAPS + tg * TPS) * 4 * a.c_out + n0) * 16;
+    d.wrec = (TPS * 4 * a.c_out - n0) * 16;
+  }
+  __device__ __forceinline__ void piece(const Dma& d, int p) const {
+    if (p < NX) {
+      if (d.do_x && p * NWV + wv < XWP) {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)d.xsrc, 0, d.xrec, 0x00020000);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (SFVOS_LDS void*)(d.xb + p * (C::NTHREADS * 16)), 16, xo[p], 0, 0, 0);
+      }
+    } else {
+      const int q = p - NX;
+      if (d.do_w && q * NWV + wv < WWP) {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)d.wsrc, 0, d.wrec, 0x00020000);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (SFVOS_LDS void*)(d.wb + q * (C::NTHREADS * 16)), 16, wo[q], 0, 0, 0);
+      }
+    }
+  }
+  __device__ __forceinline__ void issue_all(const Dma& d) const {
+#pragma unroll
+    for (int p = 0; p < NPIECE; ++p) piece(d, p);
+  }
+};
+
+// ---- epilogue: one 16-byte chunk of y (CE elements of f): optional += old, convert, store
+template <int YDT>
+__device__ __forceinline__ void store_chunk(typename Elt<YDT>::type* dst, float* f, int accumulate) {  // f[CE of y]
+  typedef typename Elt<YDT>::type T;
+  constexpr int CEY = Elt<YDT>::CE;
+  if (accumulate) {
+    const u32x4 old = *(const u32x4*)dst;
+    T oldv[CEY];
+    __builtin_memcpy(oldv, &old, 16);
+#pragma unroll
+    for (int u = 0; u < CEY; ++u) f[u] += Elt<YDT>::to_f32(oldv[u]);
+  }
+  T outv[CEY];
+#pragma unroll
+  for (int u = 0; u < CEY; ++u) outv[u] = Elt<YDT>::from_f32(f[u]);
+  u32x4 o;
+  __builtin_memcpy(&o, outv, 16);
+  *(u32x4*)dst = o;
+}
+
+// CIN: compile-time c_in (0 = runtime): a constant chunk count.  Only the frame-split kernels are dispatched with
+// CIN = 256 (fast_conv1 forward, identifiable by its own symbol in a rocprofv3 kernel trace); launch<> below always
+// passes 0, and the parameter stays so that the wide kernel's symbols remain comparable with profiles/.
 // (the body is a __device__ function: the buffer-descriptor type it uses exists only in device compilation)
 template <int DT, int TAPS, int TPS, int TT, int MT, int NT, int WS, int WN, int CIN>
 __device__ __forceinline__ void conv3d_body(const ConvArgs& a) {
@@ -120,10 +247,8 @@ __device__ __forceinline__ void conv3d_body(const ConvArgs& a) {
   constexpr bool F8 = DT == SFVOS_FP8;
   constexpr int YDT = YOf<DT>::DTY;
   typedef typename Elt<YDT>::type T;   // element type of y
-  constexpr int CE = Elt<DT>::CE, CEY = Elt<YDT>::CE, CK = 4 * CE;
+  constexpr int CE = Elt<DT>::CE, CK = 4 * CE;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* const ring = smem;
-  char* const wbase = smem + C::R * C::X_BYTES;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -161,12 +286,7 @@ __device__ __forceinline__ void conv3d_body(const ConvArgs& a) {
   const int nb = bn % a.n_blocks, b = bn / a.n_blocks;
   const int th = tile / tiles_w, tw = tile - th * tiles_w;
   const int h0 = th * C::TH, w0 = tw * C::TW, n0 = nb * C::BN, tb0 = a.t_first + tb * TT;
-
   const int ncc = (CIN ? CIN : a.c_in) / CK;
-  const long long HWp = (long long)H * W;
-  // frame 0 of this clip inside the x buffer (t_alloc frames per clip, the conv's window starts at t_offset)
-  const long long xfs_bytes = a.lv.xfs[lvl] * a.x_pitch_bytes;  // bytes between consecutive frames of this level
-  const char* xclip = a.x + (a.lv.xpos[lvl] + b * a.lv.xbs[lvl]) * a.x_pitch_bytes;
 
   f32x16 acc[M16 ? 1 : TT][M16 ? 1 : MT][M16 ? 1 : NT];
   f32x4 acc4[M16 ? TT : 1][M16 ? MT : 1][M16 ? NT : 1][2][2];  // M16: [pixel half][channel half] blocks of the tile
@@ -182,24 +302,10 @@ __device__ __forceinline__ void conv3d_body(const ConvArgs& a) {
           else acc[j][i][q][e] = 0.f;
         }
 
-  // ---- staging: buffer_load ... lds with per-lane offsets fixed for the whole kernel (see conv3d_fs_kernel):
-  // padding pixels / frames outside the clip are zero-filled by the descriptor's range check.  Pixel-major halo
-  // image, slot = (row*HC + col)*4 + (chunk ^ ((col>>2)&3)): four consecutive lanes copy one pixel's 64-byte
-  // run (coalesced) and the 16 lanes of a ds_read_b128 group still cover all 64 banks.
-  constexpr int XWP = (C::X_SLOTS + 63) / 64, WWP = (C::W_SLOTS + 63) / 64;  // 64-slot wave-pieces
-  constexpr int NWV = C::NWAVES;
-  constexpr int NX = (XWP + NWV - 1) / NWV, NW = (WWP + NWV - 1) / NWV;
-  constexpr unsigned OOB = 0x80000000u;
-  unsigned xo[NX], wo[NW];
-#pragma unroll
-  for (int it = 0; it < NX; ++it) {
-    const int sl = it * C::NTHREADS + tid;
-    const int cq = sl & 3, rc = sl >> 2, col = rc % C::HC, row = rc / C::HC;
-    const int j = cq ^ ((col >> 2) & 3);
-    const int h = h0 + row - C::HALO, w = w0 + col - C::HALO;
-    const bool ok = sl < C::X_SLOTS && (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
-    xo[it] = ok ? (unsigned)(((long long)h * W + w) * a.x_pitch_bytes + j * 16) : OOB;
-  }
+  // ---- staging: halo images with the (col>>2)&3 swizzle, for the 32x32 and the (transposed, see below) M16 fragments
+  typedef Staging<C, C::HALO, TAPS, TPS, false> Stg;
+  const Stg stg(a, smem, tid, wv, lvl, b, h0, w0, n0, tb0);
+  constexpr int NPIECE = Stg::NPIECE;
   int xsw[2][C::HALO ? 3 : 1];  // lane part of an A-fragment address: k-step st, column shift dw
 #pragma unroll
   for (int st = 0; st < 2; ++st)
@@ -218,64 +324,15 @@ __device__ __forceinline__ void conv3d_body(const ConvArgs& a) {
     const int px = 4 * (p16 & 3) + (p16 >> 2) + dw;
     xsw16[dw] = (px * 4 + (kg ^ ((px >> 2) & 3))) * 16;
   }
-#pragma unroll
-  for (int it = 0; it < NW; ++it) {
-    const int sl = it * C::NTHREADS + tid;
-    const int tj = sl / C::BN, n = sl - tj * C::BN;  // tj = tap_local*4 + chunk
-    wo[it] = (sl < C::W_SLOTS && n0 + n < a.c_out) ? (unsigned)((tj * a.c_out + n) * 16) : OOB;
-  }
-  const int lds_wave_off = wv * 1024;
-  const int frame_bytes = (int)(HWp * a.x_pitch_bytes);
-
-  struct Dma {
-    const char* xsrc; char* xb; int xrec; bool do_x;
-    const char* wsrc; char* wb; int wrec; bool do_w;
-  };
-  constexpr int NPIECE = NX + NW;
-  auto wrap = [](int sl) { return sl >= C::R ? sl - C::R : sl; };
-  auto prep_frame = [&](Dma& d, int cc, int i, int slot) {  // halo tile of input frame i, chunk cc -> ring slot
-    const int t = tb0 - a.pad_t + i, ft = a.t_offset + t;  // frame of the conv's window / of the x buffer
-    // outside the window (temporal padding) or outside the buffer (zero frames "by pointer", model.py:215-225):
-    // an empty descriptor, the copy writes zeros
-    const bool t_ok = (unsigned)t < (unsigned)a.t_in && (unsigned)ft < (unsigned)a.t_alloc;
-    d.do_x = true;
-    d.xrec = t_ok ? frame_bytes - (a.x_pitch_bytes > 64 ? cc * 64 : 0) : 0;
-    d.xb = ring + slot * C::X_BYTES + lds_wave_off;
-    d.xsrc = xclip + (long long)(t_ok ? ft : 0) * xfs_bytes + cc * a.x_chunk_bytes;
-  };
-  auto prep_w = [&](Dma& d, int cc, int dt, int tg, int s) {  // weight slice of stage s: [TPS taps][4 chunks][BN]
-    d.do_w = true;
-    d.wb = wbase + (s & 1) * C::W_BYTES + lds_wave_off;
-    d.wsrc = a.wp + (((long long)(cc * a.kt + dt) * TAPS + tg * TPS) * 4 * a.c_out + n0) * 16;
-    d.wrec = (TPS * 4 * a.c_out - n0) * 16;
-  };
-  auto piece = [&](const Dma& d, int p) {
-    if (p < NX) {
-      if (d.do_x && p * NWV + wv < XWP) {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)d.xsrc, 0, d.xrec, 0x00020000);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (SFVOS_LDS void*)(d.xb + p * (C::NTHREADS * 16)), 16, xo[p], 0, 0, 0);
-      }
-    } else {
-      const int q = p - NX;
-      if (d.do_w && q * NWV + wv < WWP) {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)d.wsrc, 0, d.wrec, 0x00020000);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (SFVOS_LDS void*)(d.wb + q * (C::NTHREADS * 16)), 16, wo[q], 0, 0, 0);
-      }
-    }
-  };
-  auto issue_all = [&](const Dma& d) {
-#pragma unroll
-    for (int p = 0; p < NPIECE; ++p) piece(d, p);
-  };
 
   // ---- one stage of MFMAs (+ the next stage's DMA, interleaved) -------------------------------------
   auto compute = [&](int tg, int s, int fslot, const Dma& d) {
     // per-stage operand bases: lane part + ring slot / weight buffer; every read below adds only a
     // compile-time constant, which folds into the ds_read offset field (no VALU per read)
-    const char* wbl = wbase + (s & 1) * C::W_BYTES + (hh * C::BN + wn * NT * 32 + r) * 16;
+    const char* wbl = stg.wbase + (s & 1) * C::W_BYTES + (hh * C::BN + wn * NT * 32 + r) * 16;
     const char* xfl[TT];
 #pragma unroll
-    for (int j = 0; j < TT; ++j) xfl[j] = ring + wrap(fslot + j) * C::X_BYTES + ws * MT * C::HC * 64;
+    for (int j = 0; j < TT; ++j) xfl[j] = stg.ring + Stg::wrap(fslot + j) * C::X_BYTES + ws * MT * C::HC * 64;
     // k-step k = (tap_local, st): a PD-deep register pipeline -- the fragments of step k+PD-1 are read
     // from LDS while the MFMAs of step k run, so the wait in front of a step never covers reads that
     // were issued just before it (counted lgkmcnt, not lgkmcnt(0)).
@@ -292,7 +349,7 @@ __device__ __forceinline__ void conv3d_body(const ConvArgs& a) {
       constexpr int NSET = 4 * TPS, NQ = 4 * TPS;
       constexpr int PPQ = (NPIECE + NQ - 1) / NQ;  // DMA pieces per quadrant step
       const int dh = (TAPS == 9) ? tg : 0;
-      const char* wbl16 = wbase + (s & 1) * C::W_BYTES + (kg * C::BN + wn * NT * 32 + p16) * 16;
+      const char* wbl16 = stg.wbase + (s & 1) * C::W_BYTES + (kg * C::BN + wn * NT * 32 + p16) * 16;
       const char* xf16[TT];
 #pragma unroll
       for (int j = 0; j < TT; ++j) xf16[j] = xfl[j] + dh * C::HC * 64;
@@ -339,7 +396,7 @@ __device__ __forceinline__ void conv3d_body(const ConvArgs& a) {
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int u = 0; u < PPQ; ++u)
-          if (k * PPQ + u < NPIECE) piece(d, k * PPQ + u);
+          if (k * PPQ + u < NPIECE) stg.piece(d, k * PPQ + u);
       }
       return;
     }
@@ -349,10 +406,6 @@ __device__ __forceinline__ void conv3d_body(const ConvArgs& a) {
     constexpr int PPS = (NPIECE + KS - 1) / KS;  // DMA pieces per k-step
     u32x4 bv[F8 ? 1 : PD][NT], av[F8 ? 1 : PD][TT][MT];
     i32x8 bv8[F8 ? PD : 1][NT], av8[F8 ? PD : 1][TT][MT];
-    auto read8 = [&](const char* lo, const char* hi) {
-      const i32x4 l = __builtin_bit_cast(i32x4, lds_read16(lo)), h = __builtin_bit_cast(i32x4, lds_read16(hi));
-      return __builtin_shufflevector(l, h, 0, 1, 2, 3, 4, 5, 6, 7);
-    };
     auto load = [&](int k, int buf) {
 #ifdef SFVOS_ABLATE  // timing-only builds (scratch): 1 = no A re-reads, 2 = no B re-reads, 3 = neither
       const bool skip_a = (SFVOS_ABLATE & 1) && k > 1, skip_b = (SFVOS_ABLATE & 2) && k > 1;
@@ -411,15 +464,13 @@ __device__ __forceinline__ void conv3d_body(const ConvArgs& a) {
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int u = 0; u < PPS; ++u)
-        if (k * PPS + u < NPIECE) piece(d, k * PPS + u);
+        if (k * PPS + u < NPIECE) stg.piece(d, k * PPS + u);
     }
   };
 
   // ---- main loop -------------------------------------------------------------------------------------
-  // Temporal taps that can touch a real frame for this frame block: with temporal zero padding
-  // (data-gradient convs, pad_t = kt-1) most (dt, frame) pairs of a block are padding -- skip them.
-  const int dt_lo = max(0, a.pad_t - tb0 - (TT - 1));
-  const int dt_hi = min(a.kt - 1, a.pad_t - tb0 + a.t_in - 1);
+  const TapRange taps = live_taps(a.pad_t, a.kt, a.t_in, tb0, TT - 1);
+  const int dt_lo = taps.lo, dt_hi = taps.hi;
   const int S = ncc * max(0, dt_hi - dt_lo + 1) * C::NTG;
   int s = 0;
   // The second-dispatched half of the workgroup loses VALU/LDS issue arbitration to its older SIMD
@@ -430,12 +481,12 @@ __device__ __forceinline__ void conv3d_body(const ConvArgs& a) {
   if (S > 0) {    // first chunk: its first TT frames and the first weight slice
     for (int i = 0; i < TT; ++i) {
       Dma d; d.do_w = false;
-      prep_frame(d, 0, dt_lo + i, wrap(fslot + i));
-      issue_all(d);
+      stg.prep_frame(d, 0, dt_lo + i, Stg::wrap(fslot + i));
+      stg.issue_all(d);
     }
     Dma d; d.do_x = false;
-    prep_w(d, 0, dt_lo, 0, 0);
-    issue_all(d);
+    stg.prep_w(d, 0, dt_lo, 0, 0);
+    stg.issue_all(d);
   }
   for (int cc = 0; cc < ncc && S > 0; ++cc) {
     for (int dt = dt_lo; dt <= dt_hi; ++dt) {
@@ -451,26 +502,26 @@ __device__ __forceinline__ void conv3d_body(const ConvArgs& a) {
           if (tg == 0 && dt == dt_hi && cc + 1 < ncc && !SFVOS_DBG(4)) {
             for (int i = 0; i < TT; ++i) {
               Dma e; e.do_w = false;
-              prep_frame(e, cc + 1, dt_lo + i, wrap(fslot + TT + i));
-              issue_all(e);
+              stg.prep_frame(e, cc + 1, dt_lo + i, Stg::wrap(fslot + TT + i));
+              stg.issue_all(e);
             }
           }
           // next frame goes into the slot freed by frame dt-1; next stage's weights into the other buffer
-          if (tg == 0 && dt < dt_hi && !SFVOS_DBG(4)) prep_frame(d, cc, dt + TT, wrap(fslot + TT));
+          if (tg == 0 && dt < dt_hi && !SFVOS_DBG(4)) stg.prep_frame(d, cc, dt + TT, Stg::wrap(fslot + TT));
           if (s + 1 < S && !SFVOS_DBG(8)) {
             int ntg = tg + 1, ndt = dt, ncc2 = cc;
             if (ntg == C::NTG) { ntg = 0; if (++ndt > dt_hi) { ndt = dt_lo; ++ncc2; } }
-            prep_w(d, ncc2, ndt, ntg, s + 1);
+            stg.prep_w(d, ncc2, ndt, ntg, s + 1);
           }
         }
         SFVOS_STAMP_AT(1)
         if (!SFVOS_DBG(1)) compute(tg, s, fslot, d);
-        else issue_all(d);
+        else stg.issue_all(d);
         SFVOS_STAMP_AT(2)
       }
-      fslot = wrap(fslot + 1);
+      fslot = Stg::wrap(fslot + 1);
     }
-    fslot = wrap(fslot + TT - 1);  // the next chunk's first frame sits behind this chunk's last TT frames
+    fslot = Stg::wrap(fslot + TT - 1);  // the next chunk's first frame sits behind this chunk's last TT frames
   }
 
   if constexpr (M16) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");  // the last asm MFMAs' D -> the epilogue's VALU reads
@@ -487,7 +538,7 @@ __device__ __forceinline__ void conv3d_body(const ConvArgs& a) {
   const long long yfs = a.lv.yfs[lvl];
   __syncthreads();  // every wave has finished reading the ring / weight buffers
   float* scr = (float*)smem + wv * (32 * 33);  // [32 px][32 ch], rows padded to 33 floats
-  constexpr int CPP = 32 / CEY;                 // 16-byte output chunks per pixel of a tile
+  constexpr int CEY = Elt<YDT>::CE, CPP = 32 / CEY;  // 16-byte output chunks per pixel of a tile
 #pragma unroll
   for (int q = 0; q < NT; ++q) {
     const int nbase = n0 + (wn * NT + q) * 32;
@@ -534,22 +585,7 @@ __device__ __forceinline__ void conv3d_body(const ConvArgs& a) {
           float f[CEY];
 #pragma unroll
           for (int u = 0; u < CEY; ++u) f[u] = scr[px * 33 + ch + u];
-          if (w0 + px < W) {
-            T* dst = yrow + (long long)px * a.ld_y + ch;
-            if (a.accumulate) {
-              const u32x4 old = *(const u32x4*)dst;
-              T oldv[CEY];
-              __builtin_memcpy(oldv, &old, 16);
-#pragma unroll
-              for (int u = 0; u < CEY; ++u) f[u] += Elt<YDT>::to_f32(oldv[u]);
-            }
-            T outv[CEY];
-#pragma unroll
-            for (int u = 0; u < CEY; ++u) outv[u] = Elt<YDT>::from_f32(f[u]);
-            u32x4 o;
-            __builtin_memcpy(&o, outv, 16);
-            *(u32x4*)dst = o;
-          }
+          if (w0 + px < W) store_chunk<YDT>(yrow + (long long)px * a.ld_y + ch, f, a.accumulate);
         }
       }
     }
@@ -645,11 +681,9 @@ __device__ __forceinline__ void fs_body(const ConvArgs& a, const int wg, const C
   constexpr bool F8 = DT == SFVOS_FP8;
   constexpr int YDT = YOf<DT>::DTY;
   typedef typename Elt<YDT>::type T;   // element type of y
-  constexpr int CE = Elt<DT>::CE, CEY = Elt<YDT>::CE, CK = 4 * CE, MT = C::MT, HM = C::HM;
+  constexpr int CE = Elt<DT>::CE, CK = 4 * CE, MT = C::MT, HM = C::HM;
   static_assert(!M16 || DT == SFVOS_BF16, "16x16x32 is the bf16 path");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* const ring = smem;
-  char* const wbase = smem + C::R * C::X_BYTES;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -672,12 +706,8 @@ __device__ __forceinline__ void fs_body(const ConvArgs& a, const int wg, const C
   const int b = grp / tgroups;
   const int th = tile / tiles_w, tw = tile - th * tiles_w;
   const int h0 = th * C::TH, w0 = tw * C::TW, tb0 = pt.t_first + tb * TT;
-
   const int NF = TT + a.kt - 1;
   const int ncc = (CIN ? CIN : a.c_in) / CK;
-  const long long HWp = (long long)H * W;
-  const long long xfs_bytes = a.lv.xfs[lvl] * a.x_pitch_bytes;  // bytes between consecutive frames of this level
-  const char* xclip = a.x + (a.lv.xpos[lvl] + b * a.lv.xbs[lvl]) * a.x_pitch_bytes;
 
   f32x16 acc[M16 ? 1 : (F8 ? HM : MT)];   // 32x32 tiles: [row]
   f32x4 acc16[M16 ? MT : 1][2];  // 16x16 tiles: [row][channel half]
@@ -690,29 +720,10 @@ __device__ __forceinline__ void fs_body(const ConvArgs& a, const int wg, const C
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc16[i][0][e] = acc16[i][1][e] = 0.f;
 
-  // ---- staging: buffer_load ... lds (LDS-DMA through a buffer descriptor).  A copy is (descriptor of the frame /
-  // weight slice, per-lane byte offset fixed for the whole kernel): padding pixels and frames outside the clip
-  // carry an out-of-range offset / an empty descriptor and the hardware range check writes zeros for them, so a
-  // piece costs two scalar instructions and no vector ALU work.  Pieces are whole wave-instructions (64 slots);
-  // wave w owns pieces w, w+8, w+16 of an image.
-  constexpr int XWP = (C::X_SLOTS + 63) / 64, WWP = (C::W_SLOTS + 63) / 64;  // wave-pieces per frame / weight slice
-  constexpr int NX = (XWP + 7) / 8, NW = (WWP + 7) / 8;
-  static_assert(C::X_BYTES >= XWP * 1024 && C::W_BYTES >= WWP * 1024, "staging images hold whole wave-pieces");
-  constexpr unsigned OOB = 0x80000000u;
-  unsigned xo[NX], wo[NW];
-#pragma unroll
-  for (int it = 0; it < NX; ++it) {
-    // pixel-major image: slot = (row*HC + col)*4 + (chunk ^ swz(col)).  Four consecutive lanes copy the four
-    // 16-byte chunks of ONE pixel (a 64-byte run of global memory), so the copy is coalesced; the XOR spreads
-    // the 16 lanes of a ds_read_b128 group over all 64 banks: swz = (col>>2)&3 for the 32x32x16 fragments (same
-    // chunk, 16 columns), 2*((col>>2)&1) for the 16x16x32 ones (two chunks x 8 columns per group).
-    const int sl = it * C::NTHREADS + tid;
-    const int cq = sl & 3, rc = sl >> 2, col = rc % C::HC, row = rc / C::HC;
-    const int j = cq ^ (M16 ? 2 * ((col >> 2) & 1) : ((col >> 2) & 3));
-    const int h = h0 + row - 1, w = w0 + col - 1;
-    const bool ok = sl < C::X_SLOTS && (unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W;
-    xo[it] = ok ? (unsigned)(((long long)h * W + w) * a.x_pitch_bytes + j * 16) : OOB;
-  }
+  // ---- staging: halo 1, whole 3x3 weight slices (wrec = 9 * 4 * c_out * 16 bytes), one channel block
+  typedef Staging<C, 1, 9, 9, M16> Stg;
+  const Stg stg(a, smem, tid, wv, lvl, b, h0, w0, 0, tb0);
+  constexpr int NPIECE = Stg::NPIECE;
   int xsw[3];  // lane part of an A-fragment address for column shift dw (chunk 2kh+hh of pixel column r+dw)
   int xsw8[2][3];  // F8: both halves of the 32-byte operand: chunks hh and 2+hh
 #pragma unroll
@@ -722,63 +733,15 @@ __device__ __forceinline__ void fs_body(const ConvArgs& a, const int wg, const C
 #pragma unroll
     for (int st = 0; st < 2; ++st) xsw8[st][dw] = ((r + dw) * 4 + ((2 * st + hh) ^ (((r + dw) >> 2) & 3))) * 16;
   }
-#pragma unroll
-  for (int it = 0; it < NW; ++it) {
-    const int sl = it * C::NTHREADS + tid;
-    const int tj = sl / C::BN, n = sl - tj * C::BN;  // tj = tap*4 + chunk
-    wo[it] = (sl < C::W_SLOTS && n < a.c_out) ? (unsigned)((tj * a.c_out + n) * 16) : OOB;
-  }
-  const int lds_wave_off = wv * 1024;
-  const int frame_bytes = (int)(HWp * a.x_pitch_bytes), wslice_bytes = 9 * 4 * a.c_out * 16;
-
-  struct Dma {
-    const char* xsrc; char* xb; int xrec; bool do_x;
-    const char* wsrc; char* wb; bool do_w;
-  };
-  constexpr int NPIECE = NX + NW;
-  auto wrap = [](int sl) { return sl >= C::R ? sl - C::R : sl; };
-  auto prep_frame = [&](Dma& d, int cc, int i, int slot) {
-    const int t = tb0 - a.pad_t + i, ft = a.t_offset + t;  // frame of the conv's window / of the x buffer
-    const bool t_ok = (unsigned)t < (unsigned)a.t_in && (unsigned)ft < (unsigned)a.t_alloc;
-    d.do_x = true;
-    // frame outside the window or outside the buffer: empty descriptor, all zeros.  (pyramid NDHWC: the chunk
-    // offset sits inside the pixel)
-    d.xrec = t_ok ? frame_bytes - (a.x_pitch_bytes > 64 ? cc * 64 : 0) : 0;
-    d.xb = ring + slot * C::X_BYTES + lds_wave_off;
-    d.xsrc = xclip + (long long)(t_ok ? ft : 0) * xfs_bytes + cc * a.x_chunk_bytes;
-  };
-  auto prep_w = [&](Dma& d, int cc, int dt, int s) {  // weight slice of stage s: [9 taps][4 chunks][32]
-    d.do_w = true;
-    d.wb = wbase + (s & 1) * C::W_BYTES + lds_wave_off;
-    d.wsrc = a.wp + ((long long)(cc * a.kt + dt) * 9 * 4 * a.c_out) * 16;
-  };
-  auto piece = [&](const Dma& d, int p) {
-    if (p < NX) {
-      if (d.do_x && p * 8 + wv < XWP) {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)d.xsrc, 0, d.xrec, 0x00020000);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (SFVOS_LDS void*)(d.xb + p * (C::NTHREADS * 16)), 16, xo[p], 0, 0, 0);
-      }
-    } else {
-      const int q = p - NX;
-      if (d.do_w && q * 8 + wv < WWP) {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)d.wsrc, 0, wslice_bytes, 0x00020000);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (SFVOS_LDS void*)(d.wb + q * (C::NTHREADS * 16)), 16, wo[q], 0, 0, 0);
-      }
-    }
-  };
-  auto issue_all = [&](const Dma& d) {
-#pragma unroll
-    for (int p = 0; p < NPIECE; ++p) piece(d, p);
-  };
 
   // ---- stage bookkeeping: stage = (channel group cc, temporal tap dt); fslot = ring slot of frame dt --------
-  const int dt_lo = max(0, a.pad_t - tb0 - (TT - 1));  // temporal taps that can touch a real frame (see conv3d_kernel)
-  const int dt_hi = min(a.kt - 1, a.pad_t - tb0 + a.t_in - 1);
+  const TapRange taps = live_taps(a.pad_t, a.kt, a.t_in, tb0, TT - 1);
+  const int dt_lo = taps.lo, dt_hi = taps.hi;
   const int S = ncc * max(0, dt_hi - dt_lo + 1);
   struct Stage { int cc, dt, fslot; };
   auto next_of = [&](const Stage& x) {
     Stage n = x;
-    if (x.dt < dt_hi) { n.dt = x.dt + 1; n.fslot = wrap(x.fslot + 1); }
+    if (x.dt < dt_hi) { n.dt = x.dt + 1; n.fslot = Stg::wrap(x.fslot + 1); }
     else { n.cc = x.cc + 1; n.dt = dt_lo; n.fslot = (n.cc * NF + dt_lo) % C::R; }
     return n;
   };
@@ -786,10 +749,10 @@ __device__ __forceinline__ void fs_body(const ConvArgs& a, const int wg, const C
   auto prep_stage = [&](Dma& d, const Stage& x, int s) {
     d.do_x = d.do_w = false;
     if (SFVOS_DBG(2)) return;
-    if (x.dt < dt_hi) prep_frame(d, x.cc, x.dt + TT, wrap(x.fslot + TT));
+    if (x.dt < dt_hi) stg.prep_frame(d, x.cc, x.dt + TT, Stg::wrap(x.fslot + TT));
     if (s + 1 < S) {
       const Stage n = next_of(x);
-      prep_w(d, n.cc, n.dt, s + 1);
+      stg.prep_w(d, n.cc, n.dt, 0, s + 1);
     }
   };
 
@@ -799,19 +762,14 @@ __device__ __forceinline__ void fs_body(const ConvArgs& a, const int wg, const C
   auto compute = [&](int s, const Stage& cur, const Dma& d, Dma& dn, const Stage& nx) {
     // F8: the wave owns rows [kh*HM, kh*HM+HM) of its row group; operand = chunks hh and 2+hh (32 bytes)
     constexpr int MTW = F8 ? HM : MT;
-    const char* wbl = wbase + (s & 1) * C::W_BYTES +
+    const char* wbl = stg.wbase + (s & 1) * C::W_BYTES +
                       (M16 ? g16 * C::BN + p16 : F8 ? hh * C::BN + r : (2 * kh + hh) * C::BN + r) * 16;
-    const char* xfl = ring + wrap(cur.fslot + jf) * C::X_BYTES + (rs * MT + (F8 ? kh * HM : 0)) * C::HC * 64;
+    const char* xfl = stg.ring + Stg::wrap(cur.fslot + jf) * C::X_BYTES + (rs * MT + (F8 ? kh * HM : 0)) * C::HC * 64;
     constexpr int ROWS = MTW + 2, NA = 3 * ROWS, PDA = 3, NH = M16 ? 2 : 1;
     constexpr int PSTRIDE = 2 * NPIECE <= NA ? 2 : 1;  // copies go out in the first steps of the stage
     static_assert(NPIECE <= NA, "DMA pieces must fit the step count");
     u32x4 av[F8 ? 1 : PDA][1], bw[F8 ? 1 : 2][3][NH];
     i32x8 av8[F8 ? PDA : 1], bw8[F8 ? 2 : 1][3];   // F8: 32-byte operands = chunks hh and 2+hh, one register octet
-    typedef __attribute__((ext_vector_type(4))) int i32x4;
-    auto read8 = [&](const char* lo, const char* hi) {
-      const i32x4 l = __builtin_bit_cast(i32x4, lds_read16(lo)), h = __builtin_bit_cast(i32x4, lds_read16(hi));
-      return __builtin_shufflevector(l, h, 0, 1, 2, 3, 4, 5, 6, 7);
-    };
     auto load_a = [&](int t) {
       const int dw = t / ROWS, rr = t - dw * ROWS;
 #ifdef SFVOS_FS_ABLATE  // timing-only builds: 1 = the pixel fragments of a stage are read once (t < PDA), 2 = the weight fragments once
@@ -882,7 +840,7 @@ __device__ __forceinline__ void fs_body(const ConvArgs& a, const int wg, const C
         }
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (t % PSTRIDE == 0 && t / PSTRIDE < NPIECE) piece(d, t / PSTRIDE);
+      if (t % PSTRIDE == 0 && t / PSTRIDE < NPIECE) stg.piece(d, t / PSTRIDE);
       if (t == 1) {
         if constexpr (STAT) dn.do_x = dn.do_w = false;
         else if (s + 1 < S) prep_stage(dn, nx, s + 1);
@@ -919,22 +877,8 @@ __device__ __forceinline__ void fs_body(const ConvArgs& a, const int wg, const C
       float f[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) f[u] = scr[px * 33 + ch + u];
-      if (w0 + kh * 16 + px < W) {
-        T* dst = yclip + (to * yfs + (long long)h * W + w0 + kh * 16 + px) * a.ld_y + ch;
-        if (a.accumulate) {
-          const u32x4 old = *(const u32x4*)dst;
-          T oldv[8];
-          __builtin_memcpy(oldv, &old, 16);
-#pragma unroll
-          for (int u = 0; u < 8; ++u) f[u] += Elt<YDT>::to_f32(oldv[u]);
-        }
-        T outv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) outv[u] = Elt<YDT>::from_f32(f[u]);
-        u32x4 o;
-        __builtin_memcpy(&o, outv, 16);
-        *(u32x4*)dst = o;
-      }
+      if (w0 + kh * 16 + px < W)
+        store_chunk<YDT>(yclip + (to * yfs + (long long)h * W + w0 + kh * 16 + px) * a.ld_y + ch, f, a.accumulate);
     }
   };
 
@@ -943,18 +887,18 @@ __device__ __forceinline__ void fs_body(const ConvArgs& a, const int wg, const C
     // the window's only real frame (t = 0 = tb0 - pad_t + i for i = pad_t: tb0 is 0 here) -> ring slot 1, once
     {
       Dma f; f.do_w = false;
-      prep_frame(f, 0, a.pad_t, 1);
-      issue_all(f);
+      stg.prep_frame(f, 0, a.pad_t, 1);
+      stg.issue_all(f);
       Dma w; w.do_x = false;
-      prep_w(w, 0, a.pad_t - pt.t_first, 0);
-      issue_all(w);
+      stg.prep_w(w, 0, a.pad_t - pt.t_first, 0, 0);
+      stg.issue_all(w);
     }
     int k = 0;
     for (int to = pt.t_first; to < pt.t_end; ++to, ++k) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();   // this frame's weight slice (and, the first time, the dy tile) landed; the other buffer is free
       Dma dw; dw.do_x = dw.do_w = false;
-      if (to + 1 < pt.t_end) prep_w(dw, 0, a.pad_t - (to + 1), k + 1);   // output frame t meets tap pad_t - t only
+      if (to + 1 < pt.t_end) stg.prep_w(dw, 0, a.pad_t - (to + 1), 0, k + 1);   // output frame t meets tap pad_t - t only
       const Stage cur{0, a.pad_t - to, 1};
       Dma dn;
       compute(k, cur, dw, dn, cur);
@@ -980,8 +924,8 @@ __device__ __forceinline__ void fs_body(const ConvArgs& a, const int wg, const C
   if (S > 0) {
     prep_stage(d, cur, 0);
     Dma w0; w0.do_x = false;
-    prep_w(w0, 0, dt_lo, 0);
-    issue_all(w0);
+    stg.prep_w(w0, 0, dt_lo, 0, 0);
+    stg.issue_all(w0);
   }
   for (; s < S; ++s) {
     if (cur.dt == dt_lo) {
@@ -990,8 +934,8 @@ __device__ __forceinline__ void fs_body(const ConvArgs& a, const int wg, const C
       if (cur.cc > 0) __syncthreads();
       for (int i = 0; i < TT; ++i) {
         Dma f; f.do_w = false;
-        prep_frame(f, cur.cc, dt_lo + i, wrap(cur.fslot + i));
-        issue_all(f);
+        stg.prep_frame(f, cur.cc, dt_lo + i, Stg::wrap(cur.fslot + i));
+        stg.issue_all(f);
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1002,7 +946,7 @@ __device__ __forceinline__ void fs_body(const ConvArgs& a, const int wg, const C
     Dma dn;
     SFVOS_STAMP_AT(1)
     if (!SFVOS_DBG(1)) compute(s, cur, d, dn, nx);
-    else { issue_all(d); if (s + 1 < S) prep_stage(dn, nx, s + 1); else dn.do_x = dn.do_w = false; }
+    else { stg.issue_all(d); if (s + 1 < S) prep_stage(dn, nx, s + 1); else dn.do_x = dn.do_w = false; }
     SFVOS_STAMP_AT(2)
     d = dn;
     cur = nx;
@@ -1059,7 +1003,7 @@ __device__ __forceinline__ void fs_body(const ConvArgs& a, const int wg, const C
   
     // ---- epilogue: rows kh*HM .. kh*HM+HM-1 of the wave's frame (as conv3d_kernel's, one channel tile) ----
     float* scr = (float*)smem + wv * (32 * 33);
-    constexpr int CPP = 32 / CEY;
+    constexpr int CEY = Elt<YDT>::CE, CPP = 32 / CEY;
     if (r < a.c_out && to < pt.t_end) {  // c_out is a multiple of 32: always true for r; kept for symmetry
       const float bias = a.bias ? a.bias[r] : 0.f;
       const float desc = F8 ? a.bias[a.c_out + r] : 1.f;  // e4m3: [2][c_out] = (bias, de-quantisation factor)
@@ -1076,32 +1020,17 @@ __device__ __forceinline__ void fs_body(const ConvArgs& a, const int wg, const C
           if (w0 + px < W) { s1 += v; s2 += v * v; }
         }
         T* yrow = yclip + (to * yfs + (long long)h * W + w0) * a.ld_y;
-  #pragma unroll
+#pragma unroll
         for (int it = 0; it < (32 * CPP) / 64; ++it) {
           const int idx = it * 64 + lane, px = idx / CPP, ch = (idx % CPP) * CEY;
           float f[CEY];
-  #pragma unroll
+#pragma unroll
           for (int u = 0; u < CEY; ++u) f[u] = scr[px * 33 + ch + u];
-          if (w0 + px < W) {
-            T* dst = yrow + (long long)px * a.ld_y + ch;
-            if (a.accumulate) {
-              const u32x4 old = *(const u32x4*)dst;
-              T oldv[CEY];
-              __builtin_memcpy(oldv, &old, 16);
-  #pragma unroll
-              for (int u = 0; u < CEY; ++u) f[u] += Elt<YDT>::to_f32(oldv[u]);
-            }
-            T outv[CEY];
-  #pragma unroll
-            for (int u = 0; u < CEY; ++u) outv[u] = Elt<YDT>::from_f32(f[u]);
-            u32x4 o;
-            __builtin_memcpy(&o, outv, 16);
-            *(u32x4*)dst = o;
-          }
+          if (w0 + px < W) store_chunk<YDT>(yrow + (long long)px * a.ld_y + ch, f, a.accumulate);
         }
       }
     }
-}
+  }
   if (a.stat_part) {
     __syncthreads();
     float* red = (float*)smem;  // [8 waves][32][2]
@@ -1328,9 +1257,8 @@ static int make_plan(const sfvos_conv_desc* d, ConvPlan* p) {
     // BN per workgroup), which restores the weight re-use the lost frames gave (slow_conv3's data gradient: 2 slots
     // instead of 4, 0.28 -> 0.17 ms; slow_conv2's: 4 instead of 5, 0.36 -> 0.31 ms).
     auto slots = [&](int tb0, int tt) {
-      const int lo = d->pad_t - tb0 - (tt - 1) > 0 ? d->pad_t - tb0 - (tt - 1) : 0;
-      const int hi = d->kt - 1 < d->pad_t - tb0 + d->t_in - 1 ? d->kt - 1 : d->pad_t - tb0 + d->t_in - 1;
-      return hi >= lo ? tt * (hi - lo + 1) : 0;
+      const TapRange r = live_taps(d->pad_t, d->kt, d->t_in, tb0, tt - 1);
+      return r.hi >= r.lo ? tt * (r.hi - r.lo + 1) : 0;
     };
     int cur = 0, single = 0;
     for (int li = 0; li < p->n_launch; ++li)
