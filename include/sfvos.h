@@ -70,7 +70,8 @@ typedef struct sfvos_levels {
  * sfvos_shift_frames / sfvos_shift_frames_stat_rows (first-layer reuse across consecutive training windows); 302 = the
  * box branch of roi_heads: sfvos_dense and its packers / gradients, sfvos_box_predictor, sfvos_fastrcnn_loss,
  * sfvos_box_decode / _encode, sfvos_detections; 303 = sfvos_relu_bwd takes any whole number of 16-byte chunks per row;
- * its twin for wide rows (the box head's) is removed. */
+ * its twin for wide rows (the box head's) is removed; 304 = the region proposal network's filter: sfvos_rpn_select /
+ * _decode / _nms (+ workspace query). */
 int sfvos_version(void);
 /* sizes[0..n) = sizeof(sfvos_conv_desc), sizeof(sfvos_pyramid), sizeof(sfvos_levels), sizeof(sfvos_mse_table),
  * sizeof(sfvos_bn_running), sizeof(sfvos_pack_item), sizeof(sfvos_planar_level) as THIS library was compiled; returns
@@ -532,6 +533,45 @@ int sfvos_detections(const float* boxes, const float* scores, const int64_t* lab
                      float score_thresh, float min_size, float nms_thresh, int max_det, float ratio_h, float ratio_w,
                      void* workspace, int* count, float* out_boxes, float* out_scores, int64_t* out_labels,
                      int* out_index, int* out_roi, sfvos_stream_t stream);
+
+/* ---- region proposal network (model.py:236-240, called at :329-335: torchvision's RegionProposalNetwork in inference,
+ * frozen and under no_grad in the reference).  The head is two existing calls: sfvos_conv3d (3x3 256 -> 256 + ReLU, kt = 1,
+ * one launch over the pyramid) and sfvos_box_predictor with num_classes = A anchors per position, which leave
+ * objectness [positions][A] and deltas [positions][4A] fp32 in the pyramid's level-major order (T = 1), i.e. torchvision's
+ * (h, w, a) flattening with segment (level l, image b) contiguous.  Segments are numbered s = l * batch + b.  The filter
+ * below restates filter_proposals, AnchorGenerator and BoxCoder(1, 1, 1, 1) (parity unpinned by the reference).
+ * Order everywhere: logit descending, ties by (level, anchor index) ascending; values compare as floats (-0 == +0, +-inf
+ * are ordinary values) and a NaN ranks below every number (torch.topk ranks it above; it can never become a proposal
+ * because its score fails the threshold).  Results are bit-identical from run to run.  Limits: pre_nms_top_n <= 4096
+ * per level, A <= 8, SFVOS_MAX_LEVELS levels; anything beyond is refused. ---- */
+
+/* Bytes of `workspace` of sfvos_rpn_nms; 0 for a refused size. */
+size_t sfvos_rpn_workspace_bytes(int n_levels, int batch, int pre_nms_top_n);
+
+/* Per segment: counts[s] = min(pre_nms_top_n, A H_l W_l) and index[s][0 .. counts[s]) = the anchor indices
+ * ((h W_l + w) A + a) of the largest logits in the order above; index[s][counts[s] .. pre_nms_top_n) = -1.
+ * counts: [n_levels * batch], index: [n_levels * batch][pre_nms_top_n] int32. */
+int sfvos_rpn_select(const float* objectness, const sfvos_pyramid* pyr, int batch, int num_anchors, int pre_nms_top_n,
+                     int* counts, int* index, sfvos_stream_t stream);
+
+/* For every (segment, rank): anchor = base_anchors[l][a] + (w stride_w, h stride_h, w stride_w, h stride_h) with
+ * stride_h = tensor_h / H_l, stride_w = tensor_w / W_l (integer division; tensor = the padded batch tensor), decoded with
+ * its 4 deltas (dw, dh clamped at `clip` = log(1000 / 16)), clipped to the image's own size image_sizes[b] = (height,
+ * width) (device floats [batch][2]); logits = the objectness logit, scores = its sigmoid; valid = both sides >= min_size
+ * and score > score_thresh.  base_anchors: device floats [n_levels][A][4].  boxes [segments][pre_nms_top_n][4], logits,
+ * scores, valid (int32) [segments][pre_nms_top_n]; ranks behind counts[s] are zeros. */
+int sfvos_rpn_decode(const float* objectness, const float* deltas, const int* counts, const int* index,
+                     const sfvos_pyramid* pyr, int batch, int num_anchors, int pre_nms_top_n, const float* base_anchors,
+                     int tensor_h, int tensor_w, const float* image_sizes, float clip, float min_size, float score_thresh,
+                     float* boxes, float* logits, float* scores, int* valid, sfvos_stream_t stream);
+
+/* Greedy NMS at IoU > nms_thresh among the valid candidates of each segment, visited in rank order (a blocked scan: 64
+ * candidates per step), then per image the survivors of all levels merged in the order above and the first
+ * post_nms_top_n kept: out_boxes [batch][post_nms_top_n][4], out_scores, out_index (= l * pre_nms_top_n + rank of the
+ * candidate) [batch][post_nms_top_n], out_count [batch]; zeros / -1 behind the count. */
+int sfvos_rpn_nms(const float* boxes, const float* logits, const float* scores, const int* valid, const int* counts,
+                  int n_levels, int batch, int pre_nms_top_n, float nms_thresh, int post_nms_top_n, void* workspace,
+                  float* out_boxes, float* out_scores, int* out_index, int* out_count, sfvos_stream_t stream);
 
 /* ---- evaluation-side reducer (reference code/helpers/davis_evaluate.py:40-42) ------------ */
 
