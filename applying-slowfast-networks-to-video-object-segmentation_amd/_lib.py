@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SFVOS_LIB') or os.path.join(_HERE, 'csrc', 'libsfvos.so')  # SFVOS_LIB: A/B builds
 
 F32, BF16, FP8 = 0, 1, 2
-ABI_REVISION = 304   # the revision of include/sfvos.h this binding mirrors
+ABI_REVISION = 305   # the revision of include/sfvos.h this binding mirrors
 MAX_LEVELS = 8
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -216,6 +216,11 @@ SIGNATURES = {
     'sfvos_rpn_decode': (i32, [vp, vp, vp, vp, C.POINTER(Pyramid), i32, i32, i32, vp, i32, i32, vp, f32, f32, f32, vp, vp,
                                vp, vp, vp]),
     'sfvos_rpn_nms': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp, vp]),
+    'sfvos_roi_match': (i32, [vp, i32, vp, vp, i32, f32, f32, vp, vp, vp, vp]),
+    'sfvos_roi_sample_workspace_bytes': (C.c_size_t, [i32]),
+    'sfvos_roi_sample': (i32, [vp, vp, vp, vp, i32, vp, i32, i32, C.c_double, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp,
+                               vp, vp, vp]),
+    'sfvos_mask_targets': (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
 }
 
 _lib = None

@@ -346,18 +346,26 @@ class RoIHeadsInference(nn.Module):
     def forward(self, features, proposals, image_shapes, original_image_sizes=None):
         """-> per image {'boxes', 'labels', 'scores', 'masks' [D,1,H,W] fp32 probabilities}; with original_image_sizes the
         boxes are resized and the masks pasted at that size (transform.postprocess)."""
-        dets = self.box.detect(features, proposals, image_shapes)
-        roi = self.mask_roi_pool(features, [d['boxes'] for d in dets], image_shapes)
-        lo = 0
-        for i, d in enumerate(dets):
-            hi = lo + d['boxes'].shape[0]
-            size = image_shapes[i]
-            if original_image_sizes is not None:
-                size = original_image_sizes[i]
-                d['boxes'] = resize_boxes(d['boxes'], image_shapes[i], size)
-            d['masks'] = self.mask.predict(roi[lo:hi], d['labels'], d['boxes'], size)
-            lo = hi
-        return dets
+        return detect_with_masks(self.box, self.mask_roi_pool, self.mask, features, proposals, image_shapes,
+                                 original_image_sizes)
+
+
+@torch.no_grad()
+def detect_with_masks(box, mask_roi_pool, mask, features, proposals, image_shapes, original_image_sizes=None):
+    """roi_heads in evaluation (+ transform.postprocess) on a BoxBranch, the mask RoIAlign and a MaskBranch: the body
+    RoIHeadsInference and roi_heads.RoIHeads share."""
+    dets = box.detect(features, proposals, image_shapes)
+    roi = mask_roi_pool(features, [d['boxes'] for d in dets], image_shapes)
+    lo = 0
+    for i, d in enumerate(dets):
+        hi = lo + d['boxes'].shape[0]
+        size = image_shapes[i]
+        if original_image_sizes is not None:
+            size = original_image_sizes[i]
+            d['boxes'] = resize_boxes(d['boxes'], image_shapes[i], size)
+        d['masks'] = mask.predict(roi[lo:hi], d['labels'], d['boxes'], size)
+        lo = hi
+    return dets
 
 
 def resize_boxes(boxes, original_size, new_size):

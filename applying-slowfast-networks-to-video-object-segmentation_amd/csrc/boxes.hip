@@ -133,17 +133,7 @@ __global__ __launch_bounds__(256) void box_encode_kernel(const float* __restrict
                                                          int M, float wx, float wy, float ww, float wh, float* targets) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= M) return;
-  const float* p = props + 4 * (long long)i;
-  const float* g = ref + 4 * (long long)i;
-  const float pw = p[2] - p[0], ph = p[3] - p[1];
-  const float pcx = p[0] + __fmul_rn(0.5f, pw), pcy = p[1] + __fmul_rn(0.5f, ph);
-  const float gw = g[2] - g[0], gh = g[3] - g[1];
-  const float gcx = g[0] + __fmul_rn(0.5f, gw), gcy = g[1] + __fmul_rn(0.5f, gh);
-  float* t = targets + 4 * (long long)i;
-  t[0] = __fmul_rn(wx, gcx - pcx) / pw;
-  t[1] = __fmul_rn(wy, gcy - pcy) / ph;
-  t[2] = __fmul_rn(ww, logf(gw / pw));
-  t[3] = __fmul_rn(wh, logf(gh / ph));
+  box_encode_one(ref + 4 * (long long)i, props + 4 * (long long)i, wx, wy, ww, wh, targets + 4 * (long long)i);
 }
 
 // transform.resize_boxes

@@ -1,6 +1,7 @@
 // Helpers shared by the HBM-bound kernels (elementwise.hip, batchnorm.hip, maskhead.hip, window_shift.hip) and the
-// roi_heads files (project.hip, boxes.hip): 16-byte pack/unpack, deterministic column and block sums; on the host, the
-// f32 / bf16 activation checks, the class-count check and dtype dispatch.
+// roi_heads files (project.hip, boxes.hip, rpn.hip, roi_targets.hip): 16-byte pack/unpack, deterministic column and block
+// sums, the block prefix scan, the box encoder; on the host, the f32 / bf16 activation checks, the class-count check and
+// dtype dispatch.
 #pragma once
 #include <type_traits>
 
@@ -90,6 +91,39 @@ __device__ __forceinline__ double block_sum_1024(double* red, double v) {
     __syncthreads();
   }
   return red[0];
+}
+
+// exclusive prefix sum over the 1024 threads of a block (thread order); wsum: 16 ints of LDS
+__device__ __forceinline__ int block_excl_scan_1024(int v, int* wsum) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(inc, o);
+    if (lane >= o) inc += u;
+  }
+  if (lane == 63) wsum[wave] = inc;
+  __syncthreads();
+  int base = 0;
+  for (int w = 0; w < wave; ++w) base += wsum[w];
+  __syncthreads();
+  return base + inc - v;
+}
+
+// BoxCoder.encode_single of one box: t[0..4) = targets of the reference box g against the proposal p (boxes.hip's
+// sfvos_box_encode and roi_targets.hip's sampler).  The products and sums are written one by one as torch issues them;
+// the compiler may still fuse `p[0] + 0.5 pw` and its three siblings into multiply-adds (the _rn intrinsics are plain
+// operators to it), which changes nothing: scaling by 0.5 is exact, so the fused and the separate form round the same sum.
+__device__ __forceinline__ void box_encode_one(const float* g, const float* p, float wx, float wy, float ww, float wh,
+                                               float* t) {
+  const float pw = p[2] - p[0], ph = p[3] - p[1];
+  const float pcx = p[0] + __fmul_rn(0.5f, pw), pcy = p[1] + __fmul_rn(0.5f, ph);
+  const float gw = g[2] - g[0], gh = g[3] - g[1];
+  const float gcx = g[0] + __fmul_rn(0.5f, gw), gcy = g[1] + __fmul_rn(0.5f, gh);
+  t[0] = __fmul_rn(wx, gcx - pcx) / pw;
+  t[1] = __fmul_rn(wy, gcy - pcy) / ph;
+  t[2] = __fmul_rn(ww, logf(gw / pw));
+  t[3] = __fmul_rn(wh, logf(gh / ph));
 }
 
 static inline unsigned grid_for(long long work_items, int per_block, unsigned cap = 2048u * 4u) {

@@ -36,23 +36,6 @@ __device__ __forceinline__ unsigned rpn_key(float v) {
   return (u >> 31) ? ~u : (u | 0x80000000u);
 }
 
-// exclusive prefix sum over the 1024 threads of a block (thread order); wsum: 16 ints of LDS
-__device__ __forceinline__ int block_excl_scan_1024(int v, int* wsum) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(inc, o);
-    if (lane >= o) inc += u;
-  }
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int base = 0;
-  for (int w = 0; w < wave; ++w) base += wsum[w];
-  __syncthreads();
-  return base + inc - v;
-}
-
 // ---- select: one workgroup per segment -----------------------------------------------------------------------------------
 // Radix select of the K-th largest key (K = min(k, n)) in three passes of 11 + 11 + 10 bits, each a histogram of the keys
 // that share the prefix found so far; then one pass that copies the keys above the K-th and the lowest-index ties of it

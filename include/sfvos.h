@@ -71,7 +71,8 @@ typedef struct sfvos_levels {
  * box branch of roi_heads: sfvos_dense and its packers / gradients, sfvos_box_predictor, sfvos_fastrcnn_loss,
  * sfvos_box_decode / _encode, sfvos_detections; 303 = sfvos_relu_bwd takes any whole number of 16-byte chunks per row;
  * its twin for wide rows (the box head's) is removed; 304 = the region proposal network's filter: sfvos_rpn_select /
- * _decode / _nms (+ workspace query). */
+ * _decode / _nms (+ workspace query); 305 = the training targets of roi_heads: sfvos_roi_match, sfvos_roi_sample (+
+ * workspace query), sfvos_mask_targets. */
 int sfvos_version(void);
 /* sizes[0..n) = sizeof(sfvos_conv_desc), sizeof(sfvos_pyramid), sizeof(sfvos_levels), sizeof(sfvos_mse_table),
  * sizeof(sfvos_bn_running), sizeof(sfvos_pack_item), sizeof(sfvos_planar_level) as THIS library was compiled; returns
@@ -572,6 +573,52 @@ int sfvos_rpn_decode(const float* objectness, const float* deltas, const int* co
 int sfvos_rpn_nms(const float* boxes, const float* logits, const float* scores, const int* valid, const int* counts,
                   int n_levels, int batch, int pre_nms_top_n, float nms_thresh, int post_nms_top_n, void* workspace,
                   float* out_boxes, float* out_scores, int* out_index, int* out_count, sfvos_stream_t stream);
+
+/* ---- training targets of roi_heads (model.py:346 with targets; torchvision's select_training_samples and
+ * project_masks_on_boxes, parity unpinned by the reference).  One image per call; the candidate list of an image is its n_p
+ * proposals followed by its G ground-truth boxes (add_gt_proposals), N = n_p + G, read through the two pointers.  Limits,
+ * refused by message: N <= 8192, G <= 1024, batch_size_per_image <= 4096, M <= 64.  Bit-identical from run to run. ---- */
+
+/* box_iou + Matcher(high, low, allow_low_quality_matches = False) + the labels of assign_targets_to_proposals, for each
+ * candidate i: with the largest IoU over the ground truth (the lower index on a tie; a NaN IoU never wins),
+ *   IoU >= high: matched[i] = that index, labels[i] = gt_labels[matched[i]];
+ *   IoU <  low : matched[i] = 0, labels[i] = 0 (background);  otherwise matched[i] = 0, labels[i] = -1 (ignored);
+ * max_iou[i] (may be NULL) = that IoU.  IoU = inter / (area_a + area_b - inter) in fp32, every operation rounded on its
+ * own, as sfvos_detections and sfvos_rpn_nms compute it.  G = 0: every label, match and max_iou is 0.
+ * proposals [n_p][4], gt_boxes [G][4], gt_labels [G] int64; matched [N] int32, labels [N] int64, max_iou [N]. */
+int sfvos_roi_match(const float* proposals, int n_p, const float* gt_boxes, const int64_t* gt_labels, int G, float high,
+                    float low, int* matched, int64_t* labels, float* max_iou, sfvos_stream_t stream);
+
+/* Bytes of `workspace` of sfvos_roi_sample for n = N candidates; 0 for a refused n. */
+size_t sfvos_roi_sample_workspace_bytes(int n);
+
+/* BalancedPositiveNegativeSampler + the gathers of select_training_samples.  With #pos candidates of label >= 1 and #neg of
+ * label 0: n_pos = min(#pos, int(batch_size_per_image * positive_fraction)), n_neg = min(#neg, batch_size_per_image -
+ * n_pos); the n_pos positives with the smallest (keys[i], i) pairs are chosen (lexicographic; -0 == +0; a NaN key ranks
+ * behind every number), the negatives likewise; label -1 is never chosen.  With independent uniform keys that is a
+ * uniformly random subset without replacement, torchvision's randperm draw in distribution (not its random stream).
+ * The chosen candidates, in ascending index (torchvision's where(pos | neg)): counts[0] = S = n_pos + n_neg rows are
+ * valid in every per-row output, counts[1] = P = n_pos.  All per-row outputs hold batch_size_per_image rows:
+ *   index int32 (-1 behind row S), out_boxes [.][4], out_labels int64, out_matched int32,
+ *   regression_targets [.][4] = sfvos_box_encode's arithmetic with weights (wx, wy, ww, wh) of the box gt_boxes[matched]
+ *   (a box of zeros when G = 0, as torchvision substitutes) against the chosen box,
+ *   pos_slot int32 = the rows whose label is >= 1, ascending, P of them.
+ * Rows behind S (P for pos_slot) are left untouched, index excepted.  labels / matched: sfvos_roi_match's; keys [N]. */
+int sfvos_roi_sample(const int64_t* labels, const int* matched, const float* keys, const float* proposals, int n_p,
+                     const float* gt_boxes, int G, int batch_size_per_image, double positive_fraction, float wx, float wy,
+                     float ww, float wh, void* workspace, int* counts, int* index, float* out_boxes, int64_t* out_labels,
+                     int* out_matched, float* regression_targets, int* pos_slot, sfvos_stream_t stream);
+
+/* project_masks_on_boxes: targets[P][M][M] = roi_align(masks[:, None], [matched, boxes], (M, M), spatial_scale 1,
+ * sampling_ratio -1, aligned False)[:, 0] -- the ADAPTIVE grid sfvos_roi_align does not have: per box roi_w = max(x2 - x1,
+ * 1), bin_w = roi_w / M, grid_w = ceil(bin_w) (the same for the height); sample x = (x1 + pw bin_w) + ((ix + .5) bin_w) /
+ * grid_w in fp32, every operation rounded on its own; a sample with y < -1, y > H, x < -1 or x > W adds 0, the others are
+ * clamped at 0 and interpolated as torchvision's bilinear_interpolate does (the last row / column branch included); the
+ * sum is divided by max(grid_h grid_w, 1).  The grid is device data: any size is looped over, none refused.
+ * masks: G planes [H][W] of uint8 (masks_are_u8 != 0, what a dataset delivers) or fp32; boxes [P][4]; matched [P] int32
+ * (a value outside [0, G) gives zeros).  P = 0 is a no-op. */
+int sfvos_mask_targets(const void* masks, int masks_are_u8, int G, int H, int W, const float* boxes, const int* matched,
+                       int P, int M, float* targets, sfvos_stream_t stream);
 
 /* ---- evaluation-side reducer (reference code/helpers/davis_evaluate.py:40-42) ------------ */
 
