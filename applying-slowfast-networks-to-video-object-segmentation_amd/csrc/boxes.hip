@@ -21,10 +21,7 @@ constexpr int DET_MAX_N = 8192;
 //   losses[0] = mean_i ( logsumexp(z_i) - z_i[label_i] )
 //   losses[1] = sum_{i: label_i > 0} sum_{d < 4} smooth_l1(deltas[i][4 label_i + d] - targets[i][d]; beta) / N
 // A label outside [0, K) makes both NaN and nothing is read through it.
-__device__ __forceinline__ float smooth_l1(float d, float beta) {
-  const float a = fabsf(d);
-  return a < beta ? 0.5f * d * d / beta : a - 0.5f * beta;
-}
+// (smooth_l1: elt_util.h)
 
 __global__ __launch_bounds__(1024) void fastrcnn_loss_kernel(const float* __restrict__ logits,
                                                              const float* __restrict__ deltas,

@@ -1,6 +1,6 @@
 // Helpers shared by the HBM-bound kernels (elementwise.hip, batchnorm.hip, maskhead.hip, window_shift.hip) and the
-// roi_heads files (project.hip, boxes.hip, rpn.hip, roi_targets.hip): 16-byte pack/unpack, deterministic column and block
-// sums, the block prefix scan, the box encoder; on the host, the f32 / bf16 activation checks, the class-count check and
+// roi_heads files (project.hip, boxes.hip, rpn.hip, roi_targets.hip, rpn_targets.hip): 16-byte pack/unpack, deterministic column and block
+// sums, the block prefix scan, the box encoder, smooth-L1; on the host, the f32 / bf16 activation checks, the class-count check and
 // dtype dispatch.
 #pragma once
 #include <type_traits>
@@ -124,6 +124,12 @@ __device__ __forceinline__ void box_encode_one(const float* g, const float* p, f
   t[1] = __fmul_rn(wy, gcy - pcy) / ph;
   t[2] = __fmul_rn(ww, logf(gw / pw));
   t[3] = __fmul_rn(wh, logf(gh / ph));
+}
+
+// torch's smooth_l1_loss of one difference (boxes.hip's box loss, rpn_targets.hip's): beta = 0 is plain L1
+__device__ __forceinline__ float smooth_l1(float d, float beta) {
+  const float a = fabsf(d);
+  return a < beta ? 0.5f * d * d / beta : a - 0.5f * beta;
 }
 
 static inline unsigned grid_for(long long work_items, int per_block, unsigned cap = 2048u * 4u) {

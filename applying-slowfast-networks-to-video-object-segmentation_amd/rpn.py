@@ -12,9 +12,14 @@ as floats (-0 == +0, +-inf ordinary).  A NaN logit ranks below every number (tor
 become a proposal, because its score fails the score threshold.  Where torchvision's order is unspecified (ties,
 saturated sigmoids) this rule is the contract.
 
-Out of scope: `loss_objectness` / `loss_rpn_box_reg` (the IoU matcher and the balanced sampler draw with torch's RNG; the
-RPN is frozen, the reference only logs them): `forward` returns `{}` for the losses.  The backbone, the transform and any
-backward are out of scope too."""
+Training call (model.py:329-335 passes the targets; the two RPN losses enter the logged total_loss at :361-368): in
+training mode with targets, `forward` also returns `loss_objectness` and `loss_rpn_box_reg`, computed by
+csrc/rpn_targets.hip -- the IoU matcher with torchvision's low-quality rule, the balanced sampler, BoxCoder(1, 1, 1,
+1).encode, BCE-with-logits and smooth-L1.  The sampler draws nothing itself: the caller's key per anchor decides (the
+smallest (key, index) pairs of a class are its sample); without keys they come from `torch.rand`, which is torchvision's
+randperm draw in distribution, not its random stream.  The losses carry no gradient (the RPN is frozen).
+
+Out of scope: the backbone, the transform and any backward."""
 import ctypes
 import math
 
@@ -192,12 +197,16 @@ class RPNHead(nn.Module):
 
 
 class RegionProposalNetwork(nn.Module):
-    """torchvision's RegionProposalNetwork in inference: head, anchors, per-level top-k, decode, clip, small-box and
-    score filter, per-level NMS, the best post_nms_top_n per image.  `self.training` picks the top-n, as in torchvision.
-    Limits: pre_nms_top_n <= 4096 per level, 8 anchors per position, 8 levels."""
+    """torchvision's RegionProposalNetwork without a backward: head, anchors, per-level top-k, decode, clip, small-box
+    and score filter, per-level NMS, the best post_nms_top_n per image; in training mode with targets also the two RPN
+    losses (anchor targets, balanced sampler, BCE and smooth-L1 with `smooth_l1_beta`; 0 is the plain L1 of newer
+    torchvision releases).  `self.training` picks the top-n, as in torchvision.
+    Limits: pre_nms_top_n <= 4096 per level, 8 anchors per position, 8 levels; for the losses 1024 ground-truth boxes per
+    image, batch_size_per_image <= 4096 and fewer than 2^24 anchors per image."""
 
     def __init__(self, anchor_generator=None, head=None, pre_nms_top_n=None, post_nms_top_n=None, nms_thresh=0.7,
-                 score_thresh=0.0, min_size=1e-3, precision='fp32'):
+                 score_thresh=0.0, min_size=1e-3, precision='fp32', fg_iou_thresh=0.7, bg_iou_thresh=0.3,
+                 batch_size_per_image=256, positive_fraction=0.5, smooth_l1_beta=1.0 / 9):
         super(RegionProposalNetwork, self).__init__()
         self.anchor_generator = anchor_generator if anchor_generator is not None else AnchorGenerator()
         A = self.anchor_generator.num_anchors_per_location()[0]
@@ -209,6 +218,9 @@ class RegionProposalNetwork(nn.Module):
         self._post_nms_top_n = dict(post_nms_top_n or dict(training=2000, testing=1000))
         self.nms_thresh, self.score_thresh, self.min_size = float(nms_thresh), float(score_thresh), float(min_size)
         self._size_tables = {}
+        self.fg_iou_thresh, self.bg_iou_thresh = float(fg_iou_thresh), float(bg_iou_thresh)
+        self.batch_size_per_image, self.positive_fraction = int(batch_size_per_image), float(positive_fraction)
+        self.smooth_l1_beta = float(smooth_l1_beta)
 
     def pre_nms_top_n(self):
         return int(self._pre_nms_top_n['training' if self.training else 'testing'])
@@ -315,8 +327,87 @@ class RegionProposalNetwork(nn.Module):
             obj, dl = self.head.forward_pyramid(clip.data, clip.shapes, clip.batch, clip.frames, int(frame))
         return self.filter_proposals(obj, dl, clip.shapes, clip.batch, image_sizes, tensor_size)[:3]
 
-    def forward(self, images, features, targets=None):
-        """torchvision's call (model.py:237-238): images has `.tensors` (the padded batch) and `.image_sizes` ->
-        (list of [n_b, 4] proposals, {}): the RPN losses are out of scope."""
+    def _anchor_args(self, shapes, tensor_size, dev):
+        """(pyramid, A, anchors per image, the C arguments `pyr, A, base_anchors, tensor_h, tensor_w`)."""
+        _levels_of(self.anchor_generator, len(shapes))
+        pyr, A = _lib.make_pyramid(shapes), self.head.num_anchors
+        N = A * sum(int(h) * int(w) for h, w in shapes)
+        return pyr, A, N, (ctypes.byref(pyr), A, _ptr(self.anchor_generator.device_table(dev)), int(tensor_size[0]),
+                           int(tensor_size[1]))
+
+    def _targets_workspace(self, pyr, A, G, dev):
+        nbytes = _lib.load().sfvos_rpn_targets_workspace_bytes(ctypes.byref(pyr), A, G, self.batch_size_per_image)
+        if nbytes == 0:
+            _lib.check(-1, 'sfvos_rpn_targets_workspace_bytes')
+        return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+    def _match(self, anchor_args, gt, ws, N):
+        labels = torch.empty(N, dtype=torch.int32, device=gt.device)
+        matched = torch.empty(N, dtype=torch.int32, device=gt.device)
+        G = gt.shape[0]
+        _lib.call('sfvos_rpn_match', *anchor_args, _ptr(gt) if G else None, G, self.fg_iou_thresh, self.bg_iou_thresh, 1,
+                  _ptr(ws), _ptr(matched), _ptr(labels), None, _stream())
+        return labels, matched
+
+    @staticmethod
+    def _gt_boxes(boxes):
+        _check_gpu(boxes, 'RegionProposalNetwork')
+        return _f32(boxes).reshape(-1, 4)
+
+    @torch.no_grad()
+    def anchor_targets(self, shapes, tensor_size, gt_boxes):
+        """assign_targets_to_anchors of one image: gt_boxes [G, 4] on the device -> (labels int32 [N]: 1 positive, 0
+        background, -1 ignored; matched int32 [N]: the ground-truth index of a positive, 0 elsewhere), N = the anchors of
+        an image in torchvision's order (level, h, w, a).  Matcher(fg_iou_thresh, bg_iou_thresh,
+        allow_low_quality_matches=True); an empty gt_boxes labels everything background."""
+        gt = self._gt_boxes(gt_boxes)
+        pyr, A, N, args = self._anchor_args(shapes, tensor_size, gt.device)
+        return self._match(args, gt, self._targets_workspace(pyr, A, gt.shape[0], gt.device), N)
+
+    @torch.no_grad()
+    def compute_loss(self, objectness, deltas, shapes, batch, tensor_size, targets, keys=None):
+        """objectness [P, A], deltas [P, 4A] fp32 in level-major order (head_outputs), targets: one dict with 'boxes'
+        [G_b, 4] per image -> {'loss_objectness', 'loss_rpn_box_reg'}: 0-dim fp32 device tensors without a gradient.
+        keys: one [N] tensor per image, the sampler's order (the smallest keys of a class are sampled); None draws them
+        with torch.rand.  One branch, no host synchronisation: capturable in a graph when keys are passed.
+        `self.last_sample` keeps (counts [B, 2] = (sampled, positives), index [B, batch_size_per_image])."""
+        _check_gpu(objectness, 'RegionProposalNetwork')
+        if len(targets) != batch or (keys is not None and len(keys) != batch):
+            raise RuntimeError('one target dict (and one key tensor) per image expected')
+        dev = objectness.device
+        pyr, A, N, args = self._anchor_args(shapes, tensor_size, dev)
+        obj, dl = _f32(objectness), _f32(deltas)
+        if obj.numel() != batch * N or dl.numel() != 4 * batch * N:
+            raise RuntimeError('objectness / deltas do not hold %d images of %d anchors' % (batch, N))
+        bs = self.batch_size_per_image
+        counts = torch.empty((batch, 2), dtype=torch.int32, device=dev)
+        index = torch.empty((batch, bs), dtype=torch.int32, device=dev)
+        reg = torch.empty((batch, bs, 4), dtype=torch.float32, device=dev)
+        st = _stream()
+        for b, t in enumerate(targets):
+            gt = self._gt_boxes(t['boxes'])
+            G = gt.shape[0]
+            ws = self._targets_workspace(pyr, A, G, dev)
+            labels, matched = self._match(args, gt, ws, N)
+            k = torch.rand(N, dtype=torch.float32, device=dev) if keys is None else _f32(keys[b])
+            if k.device != dev or k.numel() != N:
+                raise RuntimeError('keys: one value per anchor (%d) on the device expected' % N)
+            _lib.call('sfvos_rpn_sample', _ptr(labels), _ptr(matched), _ptr(k), N, *args, _ptr(gt) if G else None, G, bs,
+                      self.positive_fraction, _ptr(ws), _ptr(counts[b]), _ptr(index[b]), _ptr(reg[b]), st)
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        _lib.call('sfvos_rpn_loss', _ptr(obj), _ptr(dl), ctypes.byref(pyr), batch, A, _ptr(index), _ptr(counts), _ptr(reg),
+                  bs, self.smooth_l1_beta, None, _ptr(out), st)
+        self.last_sample = (counts, index)
+        return {'loss_objectness': out[0], 'loss_rpn_box_reg': out[1]}
+
+    def forward(self, images, features, targets=None, keys=None):
+        """torchvision's call (model.py:237-238, :329-335): images has `.tensors` (the padded batch) and `.image_sizes`
+        -> (list of [n_b, 4] proposals, losses).  losses = compute_loss on the same head outputs when the module is in
+        training mode and targets are given (keys: see compute_loss), {} otherwise."""
         tensor_size = tuple(int(v) for v in images.tensors.shape[-2:])
-        return self.propose(features, list(images.image_sizes), tensor_size), {}
+        obj, dl, shapes, B = self.head_outputs(features)
+        boxes, _, count, _ = self.filter_proposals(obj, dl, shapes, B, list(images.image_sizes), tensor_size)
+        losses = {}
+        if self.training and targets is not None:
+            losses = self.compute_loss(obj, dl, shapes, B, tensor_size, targets, keys)
+        return [boxes[b, :n] for b, n in enumerate(count.tolist())], losses

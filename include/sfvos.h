@@ -72,7 +72,8 @@ typedef struct sfvos_levels {
  * sfvos_box_decode / _encode, sfvos_detections; 303 = sfvos_relu_bwd takes any whole number of 16-byte chunks per row;
  * its twin for wide rows (the box head's) is removed; 304 = the region proposal network's filter: sfvos_rpn_select /
  * _decode / _nms (+ workspace query); 305 = the training targets of roi_heads: sfvos_roi_match, sfvos_roi_sample (+
- * workspace query), sfvos_mask_targets. */
+ * workspace query), sfvos_mask_targets; 306 = the training call of the region proposal network: sfvos_rpn_match,
+ * sfvos_rpn_sample, sfvos_rpn_loss (+ workspace query). */
 int sfvos_version(void);
 /* sizes[0..n) = sizeof(sfvos_conv_desc), sizeof(sfvos_pyramid), sizeof(sfvos_levels), sizeof(sfvos_mse_table),
  * sizeof(sfvos_bn_running), sizeof(sfvos_pack_item), sizeof(sfvos_planar_level) as THIS library was compiled; returns
@@ -619,6 +620,61 @@ int sfvos_roi_sample(const int64_t* labels, const int* matched, const float* key
  * (a value outside [0, G) gives zeros).  P = 0 is a no-op. */
 int sfvos_mask_targets(const void* masks, int masks_are_u8, int G, int H, int W, const float* boxes, const int* matched,
                        int P, int M, float* targets, sfvos_stream_t stream);
+
+/* ---- training call of the region proposal network (model.py:236-240 and :329-335 with targets; loss_objectness and
+ * loss_rpn_box_reg enter total_loss at :361-368).  The RPN is frozen and the call runs under no_grad: no backward.  Restated
+ * from torchvision's assign_targets_to_anchors, Matcher(high, low, allow_low_quality_matches = True),
+ * BalancedPositiveNegativeSampler, BoxCoder(1, 1, 1, 1).encode and compute_loss (parity unpinned by the reference).
+ * Anchor n of an image is n = A (sum_{l' < l} H_l' W_l' + h W_l + w) + a -- torchvision's per-image concatenation (level,
+ * h, w, a) -- and its box is base_anchors[l][a] + (w stride_w, h stride_h, w stride_w, h stride_h) with the strides of
+ * sfvos_rpn_decode; no anchor array is ever in memory.  Objectness and deltas stay in the pyramid's level-major storage
+ * (segment (l, b) contiguous).  Matching and sampling take one image per call, the loss all images at once; nothing
+ * synchronises with the host.  Integer atomics only (a maximum, histograms, a slot counter whose order is re-ranked):
+ * bit-identical from run to run.  Limits, refused by message before any launch: A <= 8, SFVOS_MAX_LEVELS levels, G <= 1024,
+ * batch_size_per_image <= 4096, N < 2^24 anchors per image, thresholds and fraction in [0, 1], beta >= 0. ---- */
+
+/* Bytes of `workspace` of sfvos_rpn_match and sfvos_rpn_sample (one buffer serves both, one after the other); 0 for a
+ * refused size. */
+size_t sfvos_rpn_targets_workspace_bytes(const sfvos_pyramid* pyr, int num_anchors, int G, int batch_size_per_image);
+
+/* For every anchor n the largest IoU over the ground truth (fp32, every operation rounded on its own, the arithmetic of
+ * sfvos_roi_match; the lower ground-truth index on a tie; a NaN IoU never wins):
+ *   IoU >= high: labels[n] = 1, matched[n] = that index;  IoU < low: labels[n] = 0;  otherwise labels[n] = -1;
+ *   matched[n] = 0 wherever the label is not 1 (Matcher's -1 / -2 clamped at 0);  max_iou[n] (may be NULL) = that IoU.
+ * allow_low_quality != 0 is Matcher.set_low_quality_matches_, literally: with highest[g] = max_n IoU(g, n), every anchor n
+ * with IoU(g, n) == highest[g] for some g gets labels[n] = 1 and matched[n] = its OWN argmax (not g).  A ground-truth box
+ * that no anchor overlaps has highest = 0 and so marks every anchor whose IoU with it is 0.  The comparison is exact: a
+ * second launch recomputes the IoUs with the same code.  G = 0: every label, match and max_iou is 0.
+ * base_anchors: device floats [n_levels][A][4]; gt_boxes [G][4]; matched, labels int32 [N]; max_iou [N]. */
+int sfvos_rpn_match(const sfvos_pyramid* pyr, int num_anchors, const float* base_anchors, int tensor_h, int tensor_w,
+                    const float* gt_boxes, int G, float high, float low, int allow_low_quality, void* workspace,
+                    int* matched, int* labels, float* max_iou, sfvos_stream_t stream);
+
+/* BalancedPositiveNegativeSampler under sfvos_roi_sample's contract: with #pos anchors of label >= 1 and #neg of label 0,
+ * n_pos = min(#pos, int(batch_size_per_image * positive_fraction)), n_neg = min(#neg, batch_size_per_image - n_pos); of
+ * each class the anchors with the smallest (keys[i], i) pairs are chosen (-0 == +0; a NaN key ranks behind every number);
+ * label -1 is never chosen.  The selection is a radix select of the 56-bit word (key, index) over several workgroups, one
+ * launch per digit.  counts[0] = S = n_pos + n_neg, counts[1] = P = n_pos;
+ *   index int32 [batch_size_per_image]: the P positives in ascending anchor index, then the S - P negatives in ascending
+ *   anchor index (torchvision's cat([pos, neg])), -1 behind S;
+ *   regression_targets [batch_size_per_image][4]: for the first P rows sfvos_box_encode's arithmetic with weights (1, 1, 1,
+ *   1) of gt_boxes[matched] against the anchor; the other rows are left untouched.
+ * N must be the pyramid's anchors per image.  labels, matched: sfvos_rpn_match's; keys [N]. */
+int sfvos_rpn_sample(const int* labels, const int* matched, const float* keys, int N, const sfvos_pyramid* pyr,
+                     int num_anchors, const float* base_anchors, int tensor_h, int tensor_w, const float* gt_boxes, int G,
+                     int batch_size_per_image, double positive_fraction, void* workspace, int* counts, int* index,
+                     float* regression_targets, sfvos_stream_t stream);
+
+/* compute_loss over all images: index [batch][batch_size_per_image], counts [batch][2], regression_targets
+ * [batch][batch_size_per_image][4] are sfvos_rpn_sample's outputs of each image, read on the device.  With S_tot = sum S:
+ *   out[0] = sum over the sampled rows of (max(x, 0) - x z + log1p(exp(-|x|))) / S_tot, x = the anchor's logit, z = row < P
+ *   out[1] = sum over the positive rows and 4 coordinates of smooth_l1(delta - target; beta) / S_tot; beta = 0 is plain L1
+ * (torchvision releases differ between L1 and beta = 1/9).  Sums in double, fixed order, one workgroup; S_tot = 0 gives
+ * 0 / 0 as torch does.  per_sample [batch][batch_size_per_image][2] (may be NULL) receives the two terms of each sampled
+ * row (0 for the box term of a negative); rows behind S are left untouched.  An index outside [0, N) gives NaN. */
+int sfvos_rpn_loss(const float* objectness, const float* deltas, const sfvos_pyramid* pyr, int batch, int num_anchors,
+                   const int* index, const int* counts, const float* regression_targets, int batch_size_per_image,
+                   float beta, float* per_sample, float* out, sfvos_stream_t stream);
 
 /* ---- evaluation-side reducer (reference code/helpers/davis_evaluate.py:40-42) ------------ */
 
