@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SFVOS_LIB') or os.path.join(_HERE, 'csrc', 'libsfvos.so')  # SFVOS_LIB: A/B builds
 
 F32, BF16, FP8 = 0, 1, 2
-ABI_REVISION = 306   # the revision of include/sfvos.h this binding mirrors
+ABI_REVISION = 307   # the revision of include/sfvos.h this binding mirrors
 MAX_LEVELS = 8
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -226,6 +226,9 @@ SIGNATURES = {
     'sfvos_rpn_sample': (i32, [vp, vp, vp, i32, C.POINTER(Pyramid), i32, vp, i32, i32, vp, i32, i32, C.c_double, vp, vp,
                                vp, vp, vp]),
     'sfvos_rpn_loss': (i32, [vp, vp, C.POINTER(Pyramid), i32, i32, vp, vp, vp, i32, f32, vp, vp, vp]),
+    'sfvos_fpn_lateral': (i32, [vp, i64, i64, i64, i64, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, vp, i32, i32,
+                                vp]),
+    'sfvos_fpn_pool': (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
 }
 
 _lib = None

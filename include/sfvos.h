@@ -73,7 +73,8 @@ typedef struct sfvos_levels {
  * its twin for wide rows (the box head's) is removed; 304 = the region proposal network's filter: sfvos_rpn_select /
  * _decode / _nms (+ workspace query); 305 = the training targets of roi_heads: sfvos_roi_match, sfvos_roi_sample (+
  * workspace query), sfvos_mask_targets; 306 = the training call of the region proposal network: sfvos_rpn_match,
- * sfvos_rpn_sample, sfvos_rpn_loss (+ workspace query). */
+ * sfvos_rpn_sample, sfvos_rpn_loss (+ workspace query); 307 = the feature pyramid network: sfvos_fpn_lateral,
+ * sfvos_fpn_pool. */
 int sfvos_version(void);
 /* sizes[0..n) = sizeof(sfvos_conv_desc), sizeof(sfvos_pyramid), sizeof(sfvos_levels), sizeof(sfvos_mse_table),
  * sizeof(sfvos_bn_running), sizeof(sfvos_pack_item), sizeof(sfvos_planar_level) as THIS library was compiled; returns
@@ -675,6 +676,30 @@ int sfvos_rpn_sample(const int* labels, const int* matched, const float* keys, i
 int sfvos_rpn_loss(const float* objectness, const float* deltas, const sfvos_pyramid* pyr, int batch, int num_anchors,
                    const int* index, const int* counts, const float* regression_targets, int batch_size_per_image,
                    float beta, float* per_sample, float* out, sfvos_stream_t stream);
+
+/* ---- feature pyramid network (model.py:204, `maskrcnn_model.backbone(...)`: the FPN half of torchvision's
+ * BackboneWithFPN, frozen in the reference at :176-177, so inference only; restated from torchvision's
+ * FeaturePyramidNetwork + LastLevelMaxPool, parity unpinned by the reference).  The four 3x3 output convs are
+ * sfvos_conv3d (kt = 1, taps = 9, a one-level pyramid per call); the two calls below are the rest.  Bit-identical from run
+ * to run (no atomics). ---- */
+
+/* inner_blocks[i](x) + F.interpolate(top, size = (h, w), mode = 'nearest') in one pass:
+ *   y[(b h + i) w + j][n] = bias[n] + sum_c x[b][c][i][j] weight[n][c] + top[(b top_h + (i >> 1)) top_w + (j >> 1)][n]
+ * x: planar fp32 [batch][c_in][h][w] through ELEMENT strides (stride_w must be 1), read once, never copied to a
+ * channels-last form; c_in a multiple of 32.  weight: [c_out][c_in] in the compute dtype (the natural layout cast; no
+ * packer), 16-byte aligned; c_out a multiple of 32, <= 256.  bias: fp32 [c_out].  top: NULL, or the coarser level's inner
+ * map, [batch top_h top_w] positions x ld_top in the compute dtype; h must be 2 top_h or 2 top_h - 1 and w likewise (what a
+ * stride-2 body gives; exactly there `nearest` reads index >> 1).  y: channels-last, pitch ld_y >= c_out, compute dtype.
+ * dtype: SFVOS_F32 (exact-f32 MFMA) or SFVOS_BF16 (x and weight rounded to bf16, fp32 accumulation). */
+int sfvos_fpn_lateral(const float* x, int64_t stride_b, int64_t stride_c, int64_t stride_h, int64_t stride_w, int batch,
+                      int c_in, int h, int w, const void* weight, const float* bias, int c_out, const void* top,
+                      int top_h, int top_w, int ld_top, void* y, int ld_y, int dtype, sfvos_stream_t stream);
+
+/* LastLevelMaxPool = max_pool2d(kernel 1, stride 2), a subsample: dst[b][i][j][0 .. C) = src[b][2 i][2 j][0 .. C) for
+ * i < (h - 1) / 2 + 1, j < (w - 1) / 2 + 1.  src: [batch h w] positions x ld_src, dst: [batch oh ow] positions x ld_dst,
+ * both 16-byte aligned with pitches of whole 16-byte chunks; C any whole number of 16-byte chunks; f32 or bf16. */
+int sfvos_fpn_pool(const void* src, int ld_src, void* dst, int ld_dst, int batch, int h, int w, int C, int dtype,
+                   sfvos_stream_t stream);
 
 /* ---- evaluation-side reducer (reference code/helpers/davis_evaluate.py:40-42) ------------ */
 
