@@ -1,5 +1,5 @@
 """What the per-kernel GPU tests (test_gpu_kernels.py, test_gpu_maskhead_kernels.py, test_gpu_boxhead_kernels.py,
-test_gpu_bn_kernels.py) share: pointers and streams for the C ABI, pyramid buffers, level tables, guarded outputs, the
+test_gpu_bn_kernels.py, test_gpu_conv_bwd_kernels.py) share: pointers and streams for the C ABI, pyramid buffers, level tables, guarded outputs, the
 `lib` fixture and the per-element pass criterion; relmax / rel_l2 also serve the module-level GPU tests.
 
 Pass criterion, per element (never max error / max |ref|: a wrong small element hides under a large neighbour there).
@@ -60,7 +60,21 @@ y, S1, S2 per level, the ReLU y, 7 shift cases, the 512 * 512 + 37 level of bn_b
 0.996 and bn_bwd_finalize 0.9994 (the cast is the exact rounding bound: approached, not exceeded), scale / shift of
 bn_finalize 0.12 / 0.061 against the kernel's own rstd and mean, 0.18 / 0.092 against float64; bn_running_update 0.048;
 bn_apply 0.062 (fp32), 0.996 (bf16); bn_bwd_reduce 0.0045; bn_bwd_apply dx 0.087 (fp32), 0.996 (bf16), its bias rows
-0.0025, dgamma / dbeta 0.093."""
+0.0025, dgamma / dbeta 0.093.
+
+The backward half of the conv (test_gpu_conv_bwd_kernels.py, references in conv_bwd_ref.py): exactly summable operands
+throughout.  Weight gradient: x and dy in {-1, 0, 1} (any number of positions below 2^24; the largest case sums 65 520), or
+integers in [-127, 127] -- all 8 significand bits of bf16 -- where a case has at most 1000 positions (1000 * 127^2 < 2^24);
+the sum runs over positions, tiles, shares, slabs and the sixteen split groups of wgrad_reduce_kernel, all integers below
+2^24, so grad_w EQUALS float64, also accumulated onto an integer-filled grad_w, and a second run is bit-identical.  Data
+gradient: dy and w in {-1, 0, 1}, about 432 non-zero weights per element of dx, dx an integer of |v| <= 256 with and
+without the accumulate prefill in [-8, 8], so the bf16 store is exact too.  The preconditions are asserted on the float64
+reference (test_conv_bwd_ref_cpu.py).  One random-operand case per precision (144 positions, normal x and dy) takes the
+criterion above with u_out = 0 and K = 144: the only place the full 24-bit fp32 operands pass through the MFMAs.
+
+Worst observed on an MI355X: every exact case equal (38 weight-gradient shapes over wgrad.hip's instances, lateral_wgrad.hip
+and wgrad_t1.hip, 56 with the precisions; 15 data-gradient shapes, 22 with the precisions, each with and without accumulate);
+the random weight gradient 0.0031 (fp32) and 0.0016 (bf16) of its bound."""
 import ctypes
 
 import numpy as np
