@@ -46,12 +46,19 @@ template <> __device__ __forceinline__ u32x4 pack<SFVOS_BF16>(const float* f) {
   return v;
 }
 
+// v_cvt_pk_fp8_f32 alone does not saturate: a value that rounds beyond 448 (and +-inf) becomes the NaN code 0x7f.  The
+// median of (v, 448, -448) clamps first; it does not keep a NaN (v_med3_f32 with a NaN operand takes min3, which
+// drops it: -448), so a NaN is passed through and stays a NaN code.  The counts are taken before the clamp.
+__device__ __forceinline__ float sat_e4m3(float v) {
+  const float c = __builtin_amdgcn_fmed3f(v, 448.f, -448.f);
+  return v != v ? v : c;
+}
 template <> __device__ __forceinline__ u32x4 pack<SFVOS_FP8>(const float* f) {  // 16 floats -> 16 e4m3 (saturating)
   u32x4 v;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * e], f[4 * e + 1], 0, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * e + 2], f[4 * e + 3], w, true);
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(sat_e4m3(f[4 * e]), sat_e4m3(f[4 * e + 1]), 0, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(sat_e4m3(f[4 * e + 2]), sat_e4m3(f[4 * e + 3]), w, true);
     v[e] = (unsigned)w;
   }
   return v;

@@ -156,12 +156,16 @@ typedef struct sfvos_pack_item {
 int sfvos_pack_weights_batch(const sfvos_pack_item* items, int n, int dtype, sfvos_stream_t stream);
 
 /* e4m3 operands (SFVOS_FP8).  Frames fp32 -> 64-channel groups of e4m3: element (t,h,w,c) = sat(src * scale) at byte
- * dst + (c/64)*group_stride + ((t*H+h)*W+w)*64 + c%64; C a multiple of 64. */
+ * dst + (c/64)*group_stride + ((t*H+h)*W+w)*64 + c%64; C a multiple of 64.
+ * sat(v), here and in the two calls below: v rounded to the nearest e4m3 value, ties to the even code; every finite
+ * |v| > 448 and +-inf give +-448 (0x7e / 0xfe), never a NaN code; a NaN stays a NaN code (0x7f or 0xff); -0 keeps its
+ * sign. */
 int sfvos_frames_to_groups_fp8(const float* src, int64_t stride_t, int64_t stride_c, int64_t stride_h,
                                int64_t stride_w, void* dst, int T, int C, int H, int W, int64_t group_stride,
                                float scale, int* sat_count, sfvos_stream_t stream);
-/* sat_count (device int, may be NULL): += number of elements with |src * scale| > 448 (they saturate silently in
- * e4m3; FPN features are unbounded conv outputs, so a fixed scale must be checked against the data). */
+/* sat_count (device int, may be NULL): += number of elements with |src * scale| > 448 in fp32, +-inf included, NaN not
+ * (they saturate silently in e4m3; FPN features are unbounded conv outputs, so a fixed scale must be checked against
+ * the data). */
 
 /* *amax (device float holding a non-negative value, e.g. 0) = max(*amax, max |src|) over the strided fp32 frames:
  * calibration of the e4m3 activation scale (scale = 448 / amax with head-room).  Order-independent, deterministic. */
@@ -171,7 +175,9 @@ int sfvos_frames_absmax(const float* src, int64_t stride_t, int64_t stride_c, in
 /* conv weight fp32 [c_out][c_in][kt][kh][kw] -> e4m3 forward image for sfvos_conv3d (dtype SFVOS_FP8), quantised per
  * output channel: weight_scale[n] = 448 / max|w[n]|.  bias_descale: [3][c_out] floats: row 0 = bias (zeros when bias is
  * NULL), row 1 = 1 / (act_scale * weight_scale[n]), row 2 = weight_scale[n] (sfvos_conv3d reads rows 0 and 1).
- * c_in a multiple of 64. */
+ * weight_scale[n] = 1 for an all-zero channel.  The image holds sat(w * weight_scale[n]) as defined above: a +-inf weight
+ * makes its channel's scale 0 (every finite weight of the channel becomes 0, the infinite one NaN), a NaN weight stays
+ * a NaN code.  c_in a multiple of 64. */
 int sfvos_pack_weights_fp8(const float* w, const float* bias, void* packed, float* bias_descale, int c_out, int c_in,
                            int kt, int taps, float act_scale, sfvos_stream_t stream);
 
@@ -298,7 +304,8 @@ int sfvos_bn_apply(const void* x, int ld_x, void* y, int ld_y, int dtype, const 
 
 /* The same with an e4m3 result (BASELINE config 5: the activation becomes the e4m3 operand of the next 3x3 conv):
  * y[m][c] = sat_e4m3(act(x*scale_l + shift_l) * act_scale); x bf16 with pitch ld_x (elements), y bytes with pitch ld_y;
- * C a multiple of 16; sat_count (device int, may be NULL) += values beyond +-448 before saturation. */
+ * C a multiple of 16; sat_count (device int, may be NULL) += values beyond +-448 before saturation (+-inf included, NaN
+ * not).  sat_e4m3 is the sat() of sfvos_frames_to_groups_fp8: +-inf give +-448, a NaN stays a NaN code. */
 int sfvos_bn_apply_fp8(const void* x, int ld_x, void* y, int ld_y, const sfvos_levels* lv, int C, const float* scale,
                        const float* shift, int coef_stride, int relu, float act_scale, int* sat_count,
                        const sfvos_bn_running* running, sfvos_stream_t stream);

@@ -1,5 +1,5 @@
 """What the per-kernel GPU tests (test_gpu_kernels.py, test_gpu_maskhead_kernels.py, test_gpu_boxhead_kernels.py,
-test_gpu_bn_kernels.py, test_gpu_conv_bwd_kernels.py) share: pointers and streams for the C ABI, pyramid buffers, level tables, guarded outputs, the
+test_gpu_bn_kernels.py, test_gpu_conv_bwd_kernels.py, test_gpu_fp8_kernels.py) share: pointers and streams for the C ABI, pyramid buffers, level tables, guarded outputs, the
 `lib` fixture and the per-element pass criterion; relmax / rel_l2 also serve the module-level GPU tests.
 
 Pass criterion, per element (never max error / max |ref|: a wrong small element hides under a large neighbour there).
@@ -74,7 +74,30 @@ criterion above with u_out = 0 and K = 144: the only place the full 24-bit fp32 
 
 Worst observed on an MI355X: every exact case equal (38 weight-gradient shapes over wgrad.hip's instances, lateral_wgrad.hip
 and wgrad_t1.hip, 56 with the precisions; 15 data-gradient shapes, 22 with the precisions, each with and without accumulate);
-the random weight gradient 0.0031 (fp32) and 0.0016 (bf16) of its bound."""
+the random weight gradient 0.0031 (fp32) and 0.0016 (bf16) of its bound.
+
+The e4m3 path (test_gpu_fp8_kernels.py, references in fp8_ref.py: an OCP e4m3 codec written from the format, pinned against
+torch.float8_e4m3fn in test_fp8_ref_cpu.py).  Quantisers (sfvos_frames_to_groups_fp8, sfvos_pack_weights_fp8,
+sfvos_bn_apply_fp8): one fp32 product and one rounding to the nearest e4m3 value, ties to even, so codes and saturation
+counts EQUAL the reference -- on every e4m3 value, every midpoint and its two fp32 neighbours, 2^-10, around +-448, 1e6, 3e38,
++-inf (all +-448), NaN (a NaN code) and +-0.  Where sfvos_bn_apply_fp8 gets arbitrary fp32 coefficients, its value lies
+within 2^-22 (|x scale| + |shift|) * act_scale of float64 (the ReLU-mask interval above; act_scale a power of two), a code
+must be the encoding of one end of that interval and the count lie between the counts at the two ends; nothing is left out.
+The e4m3 conv: exactly summable operands -- x codes in {-1, 0, 1} standing for q / act_scale, weights j * 2^-k(n) with a
+pilot of +-7, so that the per-channel weight scale is a power of two, w * ws an e4m3 value and every product a multiple of 64
+below 2^24 -- make y (|y| <= 256 units of 2^-k / act_scale), S1, S2 and the ReLU run EQUAL float64; full-significand operands
+(q in [-15, 15], j in [-14, 14]) keep the accumulation term zero and leave the bf16 store, |y - ref| <= 2^-8 |ref|, S1 equal,
+S2 under `check` with u_out = 0 and K = c_in * kt * 9; one random case per conv body under `check` with u_out = 2^-8 and
+K = c_in * kt * 9 + 1 (the + 1: the rounding of the de-quantisation factor).  The weight image is opaque: a conv over one-hot
+x reads back decode(encode(w * ws)) / ws for each of its 73 728 weights.
+
+Worst observed on an MI355X: every code and count equal (9 frames_to_groups_fp8 cases; 12 exact sfvos_bn_apply_fp8 cases; the
+random ones with 0 codes outside the interval, 1-13 elements per case with two admissible codes, the count at both ends the
+same and met); the three rows of sfvos_pack_weights_fp8 and the image read back equal; every exact conv case equal (16 cases,
+y, S1, S2 and the ReLU y per level: v_mfma_scale_f32_32x32x64_f8f6f4 adds integer products below 2^24 exactly); full
+significand y 0.9961 (the rounding bound of the store: approached, not exceeded), S2 0.0005; random y 0.46 (frame-split) and
+0.59 (wide), S1 0.0009, S2 0.0001.  Before pack<SFVOS_FP8> clamped to +-448 the same tests failed: v_cvt_pk_fp8_f32 alone gave
+the NaN code 0x7f for every value that rounds beyond 448 (values up to 464 still round to 448) and for +-inf."""
 import ctypes
 
 import numpy as np
