@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SFVOS_LIB') or os.path.join(_HERE, 'csrc', 'libsfvos.so')  # SFVOS_LIB: A/B builds
 
 F32, BF16, FP8 = 0, 1, 2
-ABI_REVISION = 307   # the revision of include/sfvos.h this binding mirrors
+ABI_REVISION = 308   # the revision of include/sfvos.h this binding mirrors
 MAX_LEVELS = 8
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -229,6 +229,11 @@ SIGNATURES = {
     'sfvos_fpn_lateral': (i32, [vp, i64, i64, i64, i64, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, vp, i32, i32,
                                 vp]),
     'sfvos_fpn_pool': (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
+    'sfvos_conv2d': (i32, [vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    'sfvos_conv2d_workspace_bytes': (C.c_size_t, [i32, i32, i32, i32, i32, i32, i32, i32]),
+    'sfvos_conv2d_plan': (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
+    'sfvos_body_stem': (i32, [vp, i64, i64, i64, i64, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp]),
+    'sfvos_maxpool3x3s2': (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
 }
 
 _lib = None

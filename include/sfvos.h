@@ -74,7 +74,8 @@ typedef struct sfvos_levels {
  * _decode / _nms (+ workspace query); 305 = the training targets of roi_heads: sfvos_roi_match, sfvos_roi_sample (+
  * workspace query), sfvos_mask_targets; 306 = the training call of the region proposal network: sfvos_rpn_match,
  * sfvos_rpn_sample, sfvos_rpn_loss (+ workspace query); 307 = the feature pyramid network: sfvos_fpn_lateral,
- * sfvos_fpn_pool. */
+ * sfvos_fpn_pool; 308 = the ResNet-50 body: sfvos_conv2d (+ sfvos_conv2d_plan, sfvos_conv2d_workspace_bytes),
+ * sfvos_body_stem, sfvos_maxpool3x3s2 (5 entry points; 94 in all). */
 int sfvos_version(void);
 /* sizes[0..n) = sizeof(sfvos_conv_desc), sizeof(sfvos_pyramid), sizeof(sfvos_levels), sizeof(sfvos_mse_table),
  * sizeof(sfvos_bn_running), sizeof(sfvos_pack_item), sizeof(sfvos_planar_level) as THIS library was compiled; returns
@@ -707,6 +708,44 @@ int sfvos_fpn_lateral(const float* x, int64_t stride_b, int64_t stride_c, int64_
  * both 16-byte aligned with pitches of whole 16-byte chunks; C any whole number of 16-byte chunks; f32 or bf16. */
 int sfvos_fpn_pool(const void* src, int ld_src, void* dst, int ld_dst, int batch, int h, int w, int C, int dtype,
                    sfvos_stream_t stream);
+
+/* ---- ResNet-50 body (model.py:204, `maskrcnn_model.backbone(...)`: the `body` half of torchvision's BackboneWithFPN,
+ * frozen in the reference at :176-177, so inference only; restated from torchvision's resnet50 + FrozenBatchNorm2d, parity
+ * unpinned by the reference).  Activations are channels-last: [batch][h][w] positions x pitch, in the compute dtype
+ * (SFVOS_F32: exact-f32 MFMA, SFVOS_BF16: bf16 operands, fp32 accumulation).  Bit-identical from run to run (no atomics).
+ * ---- */
+
+/* Every conv of the bottlenecks, with the frozen norm's affine, the residual and the ReLU in its epilogue:
+ *   y[b][i][j][n] = act(scale[n] * sum_{dh,dw,c} x[b][s i + dh - p][s j + dw - p][c] W[n][c][dh][dw] + shift[n]
+ *                       + residual[b][i][j][n])
+ * taps = 1 (1x1, p = 0) or 9 (3x3, p = 1); stride s = 1 or 2; output sides (h - 1) / s + 1, (w - 1) / s + 1; pixels outside
+ * the image are zero.  c_in, c_out: multiples of 64 up to 2048.  weight: [c_out][taps][c_in] in the compute dtype (the
+ * state-dict weight permuted to (n, dh, dw, c) and cast; no packer).  scale, shift: fp32 [c_out], both required.
+ * residual: NULL or [batch oh ow] positions x ld_res in the compute dtype.  acc * scale + shift in fp32, then the residual,
+ * then ReLU (relu = 1), one rounding on the store.  Pitches are whole 16-byte chunks; every pointer 16-byte aligned.
+ * workspace: sfvos_conv2d_workspace_bytes of the same shape (0 for most; the K splits of layer4's shapes need their fp32
+ * slabs, summed in split order by a second launch); NULL is accepted where that is 0. */
+int sfvos_conv2d(const void* x, int ld_x, const void* weight, const float* scale, const float* shift, const void* residual,
+                 int ld_res, void* y, int ld_y, int batch, int h, int w, int c_in, int c_out, int taps, int stride, int relu,
+                 int dtype, void* workspace, sfvos_stream_t stream);
+size_t sfvos_conv2d_workspace_bytes(int dtype, int batch, int h, int w, int c_in, int c_out, int taps, int stride);
+/* The configuration sfvos_conv2d picks for a shape on a device of `cus` compute units (0 = the current device's): 0 = 128
+ * channels x 128 positions per workgroup, 1 = 64 x 128, 2 = 64 x 64, 5 = 64 x 64 with K split over *splits slabs (1
+ * otherwise; splits may be NULL).  A pure function of its arguments; a refused shape returns SFVOS_E_ARG. */
+int sfvos_conv2d_plan(int dtype, int batch, int h, int w, int c_in, int c_out, int taps, int stride, int cus, int* splits);
+
+/* conv1 (7x7, stride 2, pad 3, 3 -> 64, no bias) + affine + ReLU: x planar fp32 [batch][3][h][w] through ELEMENT strides
+ * (stride_w must be 1), rounded to the compute dtype in registers; y channels-last [batch oh ow] x ld_y, 64 channels.
+ * weight: [64][176] in the compute dtype, k = (c * 7 + dh) * 8 + dw with zeros at dw = 7 and behind k = 168 (the
+ * state-dict weight padded and cast; no packer). */
+int sfvos_body_stem(const float* x, int64_t stride_b, int64_t stride_c, int64_t stride_h, int64_t stride_w, int batch, int h,
+                    int w, const void* weight, const float* scale, const float* shift, void* y, int ld_y, int dtype,
+                    sfvos_stream_t stream);
+
+/* max_pool2d(kernel 3, stride 2, padding 1) channels-last: dst[b][i][j][c] = max over the window's pixels inside the image
+ * (the padding is -inf, not 0).  Layouts, pitches and alignment as sfvos_fpn_pool. */
+int sfvos_maxpool3x3s2(const void* src, int ld_src, void* dst, int ld_dst, int batch, int h, int w, int C, int dtype,
+                       sfvos_stream_t stream);
 
 /* ---- evaluation-side reducer (reference code/helpers/davis_evaluate.py:40-42) ------------ */
 
