@@ -21,10 +21,12 @@ from .rpn import AnchorGenerator, RegionProposalNetwork, RPNHead  # noqa: F401
 from .roi_heads import RoIHeads, project_masks_on_boxes, select_training_samples  # noqa: F401
 from .fpn import FeaturePyramidNetwork  # noqa: F401
 from .body import BackboneWithFPN, FrozenBatchNorm2d, ResNetBody  # noqa: F401
+from .transform import GeneralizedRCNNTransform, ImageList, MaskRCNN  # noqa: F401
 
 __all__ = ['SlowFastLayers', 'PackedClip', 'SlowFastPlan', 'FusedSGD', 'GradBucket', 'init_distributed',
            'MSEProxyLoss', 'calc_kernel_sizes', 'calc_fuse_kernel_size', 'davis_pyramid', 'union_mask', 'SlowFastStream', 'SlowFastWindows', 'MaskBranch', 'MaskRCNNHeads', 'MaskRCNNPredictor',
            'maskrcnn_inference', 'maskrcnn_loss', 'paste_masks_in_image', 'MultiScaleRoIAlign', 'roi_align', 'GraphedStep', 'BoxBranch', 'TwoMLPHead', 'FastRCNNPredictor',
            'RoIHeadsInference', 'fastrcnn_loss', 'encode_boxes', 'decode_boxes', 'resize_boxes', 'AnchorGenerator', 'RPNHead',
            'RegionProposalNetwork', 'RoIHeads', 'select_training_samples', 'project_masks_on_boxes',
-           'FeaturePyramidNetwork', 'ResNetBody', 'BackboneWithFPN', 'FrozenBatchNorm2d']
+           'FeaturePyramidNetwork', 'ResNetBody', 'BackboneWithFPN', 'FrozenBatchNorm2d', 'GeneralizedRCNNTransform', 'ImageList',
+           'MaskRCNN']

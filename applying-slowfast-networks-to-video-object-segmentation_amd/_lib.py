@@ -10,8 +10,8 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SFVOS_LIB') or os.path.join(_HERE, 'csrc', 'libsfvos.so')  # SFVOS_LIB: A/B builds
 
-F32, BF16, FP8 = 0, 1, 2
-ABI_REVISION = 308   # the revision of include/sfvos.h this binding mirrors
+F32, BF16, FP8, U8 = 0, 1, 2, 3
+ABI_REVISION = 309   # the revision of include/sfvos.h this binding mirrors
 MAX_LEVELS = 8
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -234,6 +234,9 @@ SIGNATURES = {
     'sfvos_conv2d_plan': (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
     'sfvos_body_stem': (i32, [vp, i64, i64, i64, i64, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp]),
     'sfvos_maxpool3x3s2': (i32, [vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
+    'sfvos_transform_image': (i32, [vp, i32, i64, i64, i64, i64, i32, i32, i32, f32, f32, f32, f32, f32, f32, vp, i64, i64,
+                                    i64, i32, i32, i32, i32, vp]),
+    'sfvos_transform_masks': (i32, [vp, i32, i32, i32, vp, i32, i32, vp]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 """The ResNet-50 body of the reference's backbone (code/helpers/model.py:204, `maskrcnn_model.backbone(...)`: the
 `body` half of torchvision's BackboneWithFPN) on libsfvos kernels: the normalised image tensor -> C2..C5, and with
-BackboneWithFPN on to the packed pyramid.  Only the transform (normalise, resize, batch) is left to the caller.
+BackboneWithFPN on to the packed pyramid.  The transform in front of it (normalise, resize, batch) is transform.py's; its
+batched tensor is what the stem reads.
 
 The reference freezes the backbone (model.py:176-177) and runs it under no_grad (:324), so this is inference only:
 every BatchNorm is a FrozenBatchNorm2d, a per-channel affine in the conv's epilogue.  torchvision is third-party, not
@@ -14,7 +15,7 @@ sfvos_maxpool3x3s2, then one sfvos_conv2d launch per conv of the 16 bottlenecks 
 launch), each with its frozen norm, the residual and the ReLU in the epilogue; activations stay channels-last in the
 compute dtype from the stem to C5.
 
-Out of scope: the transform, any backward, trainable or train-mode BatchNorm, other block types, e4m3."""
+Out of scope: the transform (transform.py), any backward, trainable or train-mode BatchNorm, other block types, e4m3."""
 from collections import OrderedDict
 
 import torch

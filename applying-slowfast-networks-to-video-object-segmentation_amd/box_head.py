@@ -351,9 +351,10 @@ class RoIHeadsInference(nn.Module):
 
 
 @torch.no_grad()
-def detect_with_masks(box, mask_roi_pool, mask, features, proposals, image_shapes, original_image_sizes=None):
+def detect_with_masks(box, mask_roi_pool, mask, features, proposals, image_shapes, original_image_sizes=None, paste=True):
     """roi_heads in evaluation (+ transform.postprocess) on a BoxBranch, the mask RoIAlign and a MaskBranch: the body
-    RoIHeadsInference and roi_heads.RoIHeads share."""
+    RoIHeadsInference and roi_heads.RoIHeads share.  paste=False leaves 'masks' as the [D,1,28,28] probabilities
+    (torchvision's roi_heads; transform.postprocess pastes them)."""
     dets = box.detect(features, proposals, image_shapes)
     roi = mask_roi_pool(features, [d['boxes'] for d in dets], image_shapes)
     lo = 0
@@ -363,7 +364,7 @@ def detect_with_masks(box, mask_roi_pool, mask, features, proposals, image_shape
         if original_image_sizes is not None:
             size = original_image_sizes[i]
             d['boxes'] = resize_boxes(d['boxes'], image_shapes[i], size)
-        d['masks'] = mask.predict(roi[lo:hi], d['labels'], d['boxes'], size)
+        d['masks'] = mask.predict(roi[lo:hi], d['labels'], d['boxes'], size, paste)
         lo = hi
     return dets
 

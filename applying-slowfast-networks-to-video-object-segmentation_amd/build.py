@@ -8,7 +8,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 LIB = os.path.join(CSRC, 'libsfvos.so')
-SOURCES = ['runtime.hip', 'elementwise.hip', 'batchnorm.hip', 'conv3d.hip', 'wgrad.hip', 'lateral.hip', 'lateral_wgrad.hip', 'wgrad_t1.hip', 'maskhead.hip', 'roialign.hip', 'window_shift.hip', 'dense.hip', 'boxes.hip', 'project.hip', 'rpn.hip', 'roi_targets.hip', 'rpn_targets.hip', 'fpn.hip', 'body.hip']
+SOURCES = ['runtime.hip', 'elementwise.hip', 'batchnorm.hip', 'conv3d.hip', 'wgrad.hip', 'lateral.hip', 'lateral_wgrad.hip', 'wgrad_t1.hip', 'maskhead.hip', 'roialign.hip', 'window_shift.hip', 'dense.hip', 'boxes.hip', 'project.hip', 'rpn.hip', 'roi_targets.hip', 'rpn_targets.hip', 'fpn.hip', 'body.hip', 'transform.hip']
 HEADERS = ['common.h', 'elt_util.h']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 

@@ -13,7 +13,7 @@ nearest-upsampled coarser inner map -> channels-last inner map), then one sfvos_
 the level's region of the pyramid buffer; `pool` is one sfvos_fpn_pool launch.  Between the body and the detections no
 layout pass remains.
 
-Out of scope: the ResNet body, the transform, any backward, the frame-major ring of SlowFastStream, e4m3 output, and
+Out of scope: the ResNet body (body.py), the transform (transform.py), any backward, the frame-major ring of SlowFastStream, e4m3 output, and
 B > 1 in `write_frames`."""
 import ctypes
 from collections import OrderedDict

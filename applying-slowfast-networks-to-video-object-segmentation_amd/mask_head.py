@@ -307,12 +307,15 @@ class MaskBranch(nn.Module):
         return self.mask_predictor.forward_from_nhwc(self.mask_head.forward_nhwc(roi_features))[0]
 
     @torch.no_grad()
-    def predict(self, roi_features, labels, boxes, img_shape):
+    def predict(self, roi_features, labels, boxes, img_shape, paste=True):
         """Inference path of roi_heads + transform.postprocess for one image (model.py:346-347): the detections'
         masks pasted into the image, [N,1,H,W] fp32 probabilities (thresholded at 0.5 and OR-ed by
-        davis_evaluate.py:40-42 -> sfvos_amd.union_mask)."""
+        davis_evaluate.py:40-42 -> sfvos_amd.union_mask).  paste=False: the [N,1,2M,2M] probabilities themselves, what
+        torchvision's roi_heads returns and transform.postprocess pastes."""
         if roi_features.shape[0] == 0:
+            if not paste:
+                return roi_features.new_empty((0, 1, 2 * roi_features.shape[2], 2 * roi_features.shape[3]))
             return roi_features.new_empty((0, 1, int(img_shape[0]), int(img_shape[1])))
         _, prob = self.mask_predictor.forward_from_nhwc(self.mask_head.forward_nhwc(roi_features), labels,
                                                         want_logits=False, want_prob=True)
-        return paste_masks_in_image(prob, boxes, img_shape)
+        return paste_masks_in_image(prob, boxes, img_shape) if paste else prob

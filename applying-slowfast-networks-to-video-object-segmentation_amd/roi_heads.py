@@ -146,7 +146,8 @@ class RoIHeads(nn.Module):
     forward(features, proposals, image_shapes, targets=None, keys=None) -> (detections, losses):
       training: ([], {'loss_classifier', 'loss_box_reg', 'loss_mask'}); targets: per image 'boxes', 'labels', 'masks'
                 [G,H,W]; keys: select_training_samples' (None: drawn with torch.rand);
-      eval    : (what RoIHeadsInference returns with the same weights, {}).
+      eval    : (what RoIHeadsInference returns with the same weights, {}); with `paste_masks = False` (MaskRCNN sets it)
+                'masks' are the [D,1,28,28] probabilities torchvision's roi_heads returns, for transform.postprocess.
     `score_thresh`, `nms_thresh` and `detections_per_img` are read at call time (model.py:187 sets the last one after
     construction)."""
 
@@ -168,6 +169,7 @@ class RoIHeads(nn.Module):
         self.detections_per_img = int(box_detections_per_img)
         self.batch_size_per_image, self.positive_fraction = int(box_batch_size_per_image), float(box_positive_fraction)
         self.fg_iou_thresh, self.bg_iou_thresh = float(box_fg_iou_thresh), float(box_bg_iou_thresh)
+        self.paste_masks = True     # False (MaskRCNN): 'masks' stay [D,1,28,28] for transform.postprocess, as in torchvision
 
     def _branches(self):
         box, mask = self._box, self._mask
@@ -178,7 +180,8 @@ class RoIHeads(nn.Module):
     def forward(self, features, proposals, image_shapes, targets=None, keys=None):
         box, mask = self._branches()
         if not self.training:
-            return detect_with_masks(box, self.mask_roi_pool, mask, features, proposals, image_shapes), {}
+            return detect_with_masks(box, self.mask_roi_pool, mask, features, proposals, image_shapes,
+                                     paste=self.paste_masks), {}
         check_targets(targets, need_masks=True)
         res = _sample(proposals, targets, keys, None, self.batch_size_per_image, self.positive_fraction,
                       self.fg_iou_thresh, self.bg_iou_thresh)

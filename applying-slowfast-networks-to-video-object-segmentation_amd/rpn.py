@@ -19,7 +19,8 @@ csrc/rpn_targets.hip -- the IoU matcher with torchvision's low-quality rule, the
 smallest (key, index) pairs of a class are its sample); without keys they come from `torch.rand`, which is torchvision's
 randperm draw in distribution, not its random stream.  The losses carry no gradient (the RPN is frozen).
 
-Out of scope: the backbone, the transform and any backward."""
+Out of scope: the backbone (body.py, fpn.py), the transform (transform.py; its ImageList is what `forward` takes) and any
+backward."""
 import ctypes
 import math
 

@@ -40,7 +40,8 @@ extern "C" {
 typedef void* sfvos_stream_t; /* hipStream_t */
 
 enum { SFVOS_F32 = 0, SFVOS_BF16 = 1,
-       SFVOS_FP8 = 2 /* OCP e4m3 operands; inference-only first step, see sfvos_conv_desc.dtype */ };
+       SFVOS_FP8 = 2 /* OCP e4m3 operands; inference-only first step, see sfvos_conv_desc.dtype */,
+       SFVOS_U8 = 3 /* bytes: a source dtype of sfvos_transform_image only */ };
 
 enum {
   SFVOS_OK = 0,
@@ -75,7 +76,8 @@ typedef struct sfvos_levels {
  * workspace query), sfvos_mask_targets; 306 = the training call of the region proposal network: sfvos_rpn_match,
  * sfvos_rpn_sample, sfvos_rpn_loss (+ workspace query); 307 = the feature pyramid network: sfvos_fpn_lateral,
  * sfvos_fpn_pool; 308 = the ResNet-50 body: sfvos_conv2d (+ sfvos_conv2d_plan, sfvos_conv2d_workspace_bytes),
- * sfvos_body_stem, sfvos_maxpool3x3s2 (5 entry points; 94 in all). */
+ * sfvos_body_stem, sfvos_maxpool3x3s2 (5 entry points; 94 in all); 309 = the image transform: sfvos_transform_image,
+ * sfvos_transform_masks (96 in all). */
 int sfvos_version(void);
 /* sizes[0..n) = sizeof(sfvos_conv_desc), sizeof(sfvos_pyramid), sizeof(sfvos_levels), sizeof(sfvos_mse_table),
  * sizeof(sfvos_bn_running), sizeof(sfvos_pack_item), sizeof(sfvos_planar_level) as THIS library was compiled; returns
@@ -746,6 +748,41 @@ int sfvos_body_stem(const float* x, int64_t stride_b, int64_t stride_c, int64_t 
  * (the padding is -inf, not 0).  Layouts, pitches and alignment as sfvos_fpn_pool. */
 int sfvos_maxpool3x3s2(const void* src, int ld_src, void* dst, int ld_dst, int batch, int h, int w, int C, int dtype,
                        sfvos_stream_t stream);
+
+/* ---- image transform (model.py:283, :298: `maskrcnn_model.transform(images, targets)`, torchvision's
+ * GeneralizedRCNNTransform; restated from its published sources and torch's upsample kernels, parity unpinned by the
+ * reference).  The size rule (min_size / max_size -> oh x ow, size_divisible -> Hp x Wp) lives on the host. ---- */
+
+/* normalize + resize (bilinear, align_corners = False, scale recomputed from the sizes) + batch_images' zero pad in one
+ * launch: `batch` images of h x w pixels and 3 channels -> dst[b][c][0 .. Hp)[0 .. Wp), planar fp32, which sfvos_body_stem
+ * reads.  The image occupies [0, oh) x [0, ow); every other element up to Hp x Wp is written as +0.0f (dst may be
+ * uninitialised); nothing outside [0, Hp) x [0, Wp) of a plane is touched.
+ * src: SFVOS_F32 (stride_w must be 1) or SFVOS_U8 through ELEMENT strides, so a decoded [batch][h][w][3] byte frame is
+ *   read in place (stride_c = 1, stride_w = 3); a byte u enters as float(u) / 255.0f (IEEE division: ToTensor), after
+ *   which both dtypes take the same arithmetic.  dst: 16-byte aligned, strides in elements, non-negative multiples of 4
+ *   (16-byte rows), stride 1 along w, dst_stride_h >= Wp.  mean, std: by value; every std > 0.
+ * Arithmetic of output pixel (i, j) of channel c, all in fp32, every operation rounded to nearest on its own (no fused
+ * multiply-add), in this order -- the contract:
+ *     scale = (float)in / (float)out                       (per axis: h / oh, w / ow)
+ *     src   = max(scale * ((float)d + 0.5f) - 0.5f, 0)     (d = i resp. j)
+ *     i0 = (int)src,  i1 = min(i0 + 1, in - 1),  l1 = src - (float)i0,  l0 = 1.0f - l1
+ *     v(y, x) = (x[b][c][y][x] - mean[c]) / std[c]         (IEEE division) for the four taps
+ *     left  = ly0 * v(y0, x0) + ly1 * v(y1, x0),  right = ly0 * v(y0, x1) + ly1 * v(y1, x1)     (vertically first)
+ *     out   = lx0 * left + lx1 * right
+ * Offsets are 64-bit (a sequence's batch exceeds 4 GB); a source plane and a padded plane hold fewer than 2^31
+ * elements.  Bit-identical from run to run and between the two source dtypes on equal values. */
+int sfvos_transform_image(const void* src, int src_dtype, int64_t stride_b, int64_t stride_c, int64_t stride_h,
+                          int64_t stride_w, int batch, int h, int w, float mean0, float mean1, float mean2, float std0,
+                          float std1, float std2, float* dst, int64_t dst_stride_b, int64_t dst_stride_c,
+                          int64_t dst_stride_h, int oh, int ow, int Hp, int Wp, sfvos_stream_t stream);
+
+/* The nearest resize of the target masks, F.interpolate(mask[:, None].float(), size = (oh, ow))[:, 0].byte():
+ *     dst[g][i][j] = src[g][min((int)floorf((float)i * scale_h), h - 1)][min((int)floorf((float)j * scale_w), w - 1)],
+ *     scale = (float)in / (float)out in fp32.
+ * src: dense bytes [G][h][w]; dst: dense bytes [G][oh][ow], as sfvos_mask_targets takes them.  G = 0 returns 0 without a
+ * launch (the pointers may be NULL then). */
+int sfvos_transform_masks(const unsigned char* src, int G, int h, int w, unsigned char* dst, int oh, int ow,
+                          sfvos_stream_t stream);
 
 /* ---- evaluation-side reducer (reference code/helpers/davis_evaluate.py:40-42) ------------ */
 
